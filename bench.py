@@ -19,6 +19,12 @@ sequences already resident in HBM.
           any rank fails either, ALL ranks use the pinned-host + gloo transport and the line says so ("comm",
           "comm_note").  MI355SW_BENCH_COMM=host selects that transport outright.
 Rank 0 prints ONE JSON line.  GCUPS convention of the reference: cells = m*n (sw_stage1.cpp:440-448).
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, roofline figures of the timed kernel).
+--full adds everything else, run once behind the timed steps: N = 1 the north-star-height step (target_shape), c3_shape,
+c5_shape, c3_full and the CPU baselines; N > 1 rank 0's same-shape single-GPU reference and BASELINE's multi-GPU
+configuration (c4_half / c4_full / c5_full).  --dump-outputs DIR writes what the last timed step returned, the best cell
+(0-based i, j, score), as DIR/best_cell.npy (float64).
 """
 import argparse
 import json
@@ -300,10 +306,19 @@ def main():
                     help="N > 1: skip rank 0's untimed run of ONE GPU's share of the cells (tall*size x size) alone")
     ap.add_argument("--no-full-config", action="store_true",
                     help="N = 2, 4, 8: skip BASELINE's multi-GPU configuration run once behind the timed steps (c4_half / c4_full / c5_full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extras behind the timed steps (N = 1: target_shape, c3_shape, c5_shape, c3_full, cpu_baseline; "
+                         "N > 1: same_shape_single_gpu and BASELINE's multi-GPU configuration); the --no-* options above pick among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the best cell, 0-based i, j, score) as DIR/best_cell.npy, float64")
     ap.add_argument("--launch-check", action="store_true",
                     help="only check the launcher: the ranks meet over gloo, rank 0 prints one line (runs without a GPU)")
     ap.add_argument("--launch-check-sleep", type=float, default=0.0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     # N > 1 from a plain `python3 bench.py --gpus N`: the ranks are started here, as a child process, before anything that
     # initialises the GPU has been imported (self_launch)
@@ -464,7 +479,7 @@ def main():
     # no neighbour -- so that the scaling figure compares like with like (the N = 1 line of this bench is C2, a
     # 2-round shape that is ~10 % slower per cell than a tall one).  Rank 0, untimed, before the chain.
     single_ref = None
-    if world > 1 and not args.no_single_reference:
+    if world > 1 and args.full and not args.no_single_reference:
         if rank == 0:
             # its own engine, default configuration (the strip height one GPU would pick for this shape, not the chain's),
             # the same recurrence and pruning as the chain; one untimed run first (buffers, seed pass), then the timed one
@@ -537,6 +552,11 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=coll_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the chain's best cell (0-based i, j, score), exact in float64
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "best_cell.npy"), np.array([int(x) for x in best], dtype=np.float64))
 
     ranks = None
     if world > 1:
@@ -559,7 +579,7 @@ def main():
     # BASELINE's own multi-GPU configuration for this N, once, behind the timed steps (collective: every rank takes part; whatever
     # goes wrong in it is reported inside the line, it never costs the headline)
     full_cfg, full_out = None, None
-    if world > 1 and not args.no_full_config:
+    if world > 1 and args.full and not args.no_full_config:
         full_cfg = full_config_for(world, rehearse)
     if full_cfg is not None:
         budget = float(os.environ.get("MI355SW_BENCH_EXTRAS_MAX_S", "1800"))
@@ -631,26 +651,26 @@ def main():
                                   % (st["strips"], ("%d and %d" % (st["strip_rows"], st["strip_rows_second"])) if mixed else str(st["strip_rows"])))},
             "valu_roofline": _valu(st, band_cells, k_ms, pmc),
         }
-        # the extras must never cost the headline line: whatever goes wrong in them is reported inside the JSON
-        if world == 1 and not args.no_target_shape:
+        # the extras (--full) must never cost the headline line: whatever goes wrong in them is reported inside the JSON
+        if world == 1 and args.full and not args.no_target_shape:
             try:
                 out["target_shape"] = target_shape(pkg, local_rank, check=not args.no_cpu_baseline)
             except Exception as e:                       # noqa: BLE001
                 out["target_shape"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_shapes:
+        if world == 1 and args.full and not args.no_shapes:
             for key, fn in (("c3_shape", c3_shape), ("c5_shape", c5_shape)):
                 try:
                     out[key] = fn(pkg, local_rank)
                 except Exception as e:                   # noqa: BLE001
                     out[key] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_c3_full:
+        if world == 1 and args.full and not args.no_c3_full:
             try:
                 out["c3_full"] = c3_full(pkg, local_rank)
             except Exception as e:                       # noqa: BLE001
                 out["c3_full"] = {"error": "%s: %s" % (type(e).__name__, e)}
         if full_cfg is not None:
             out[full_cfg["key"]] = full_out
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             for key, fn in (("cpu_baseline", cpu_baseline), ("cpu_baseline_all_cores", cpu_baseline_mt)):
                 try:
                     out[key] = fn(pkg)

@@ -100,3 +100,14 @@ def test_the_gpus_n_line_runs_baselines_own_multi_gpu_configuration():
     assert (rec4["best"]["i"], rec4["best"]["j"], rec4["best"]["score"]) == (c4["expect"]["i"], c4["expect"]["j"], c4["expect"]["score"])
     rec5 = json.load(open(os.path.join(ROOT, "profiles", "r05_nw_c5_249Mx228M_one_gpu_2048rows.json")))
     assert rec5["h_last_cell"] == c5["expect"]["score"]
+
+
+def test_plain_and_full_runs_and_the_output_dump_are_options():
+    """a plain run times its steps and nothing else; the extras run under --full; --dump-outputs DIR names where the last
+    timed step's result goes; --steps must ask for at least one timed step (ms_per_step is per timed step)"""
+    p = _run(["--help"])
+    assert p.returncode == 0
+    text = p.stdout.decode()
+    assert "--full" in text and "--dump-outputs DIR" in text
+    p = _run(["--gpus", "1", "--steps", "0"])
+    assert p.returncode == 2 and b"--steps must be at least 1" in p.stderr

@@ -7,8 +7,8 @@
 #                  then the tests that failed once more ALONE -- the box has 256 host cores and the suite's time is the oracle's
 #                  and Python's, not the GPU's: 140 s instead of 500 s (profiles/r05_gpu_suite_xdist_rehearsal.log); tests that
 #                  bound a run's TIME may fail next to five other processes on the GPU, hence the second, serial pass
-#   bench          python3 bench.py (the driver's N = 1 command) -> bench.json
-#   selflaunch:N   MI355SW_BENCH_REHEARSAL=1 python3 bench.py --gpus N --size 300000  (bench.py starts its own ranks; all on cuda:0)
+#   bench          python3 bench.py --full (the driver's N = 1 command with every extra) -> bench.json
+#   selflaunch:N   MI355SW_BENCH_REHEARSAL=1 python3 bench.py --gpus N --size 300000 --full  (bench.py starts its own ranks; all on cuda:0)
 #   launchcheck    bench.py --launch-check: 2 ranks (gloo on a one-GPU box), then the nccl (= RCCL) backend with one rank on the GPU
 #   rehearse       the N > 1 path of bench.py on the one GPU through every transport and recurrence (self-launched)
 #   ab:M,N[,R]     a related M x N pair: unpruned, pruned with the window, pruned without it (tools/window_probe.py)
@@ -42,7 +42,7 @@ for step in "$@"; do
         fi
         timeout 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $out/smoke.log ;;
     bench)
-        timeout 1700 python3 bench.py > $out/bench.json 2> $out/bench.err; rc=$?
+        timeout 1700 python3 bench.py --full > $out/bench.json 2> $out/bench.err; rc=$?
         python3 - <<PY
 import json
 try:
@@ -57,7 +57,7 @@ except Exception as e:
 PY
         ;;
     selflaunch)
-        MI355SW_BENCH_REHEARSAL=1 MI355SW_BENCH_TIMEOUT_S=600 python3 bench.py --gpus $arg --steps 2 --warmup 1 --size 300000 > $out/selflaunch_$arg.json 2> $out/selflaunch_$arg.err; rc=$?
+        MI355SW_BENCH_REHEARSAL=1 MI355SW_BENCH_TIMEOUT_S=600 python3 bench.py --gpus $arg --steps 2 --warmup 1 --size 300000 --full > $out/selflaunch_$arg.json 2> $out/selflaunch_$arg.err; rc=$?
         python3 -c "
 import json
 d=json.loads(open('$out/selflaunch_$arg.json').read().strip().splitlines()[-1]); c=d['config']
@@ -73,7 +73,7 @@ for k in ('c4_half', 'c4_full', 'c5_full'):
     rehearse)
         rc=0
         run() { n=$1; t=$2; shift 2
-            MI355SW_BENCH_REHEARSAL=1 MI355SW_BENCH_TIMEOUT_S=600 python3 bench.py --gpus $n --steps 2 --warmup 1 --size 300000 "$@" > $out/rehearsal_$t.json 2> $out/rehearsal_$t.err
+            MI355SW_BENCH_REHEARSAL=1 MI355SW_BENCH_TIMEOUT_S=600 python3 bench.py --gpus $n --steps 2 --warmup 1 --size 300000 --full "$@" > $out/rehearsal_$t.json 2> $out/rehearsal_$t.err
             r=$?; [ $r -ne 0 ] && rc=$r
             python3 -c "
 import json
