@@ -251,7 +251,13 @@ int mi355sw_align_partition(mi355sw_handle* h, const mi355sw_partition* partitio
  * order PER partition, all from the calling thread -- but the partitions run side by side, so the calls of different
  * managers interleave.  Every partition needs its own manager state (borders, goal, sinks).  Partitions the batch
  * cannot take (more than 14 common byte values, >= 32 Mi rows, block pruning or block scores wanted, an overflow report
- * of the packed kernel) are run one by one after the others.  mi355sw_get_stats: sums over the call. */
+ * of the packed kernel) are run one by one after the others; an overflow rerun replays what the batch attempt already
+ * took and handed over (streamed first-column cells, last-column rows, special rows), as a single call's rerun does.
+ * Special rows: the batch's strip height (mi355sw_config.batch_rows_per_lane) is the engine's own choice when the handle's
+ * rows_per_lane is 0, so the rows sit on the 2048-row grid a single call puts them on; with a fixed rows_per_lane they sit
+ * on multiples of the batch's strip height -- the single call's rows only where the two heights are equal -- and the
+ * overflow rerun of such a partition runs at the batch's height, so that all of its rows sit on that one grid.
+ * mi355sw_get_stats: sums over the call. */
 int mi355sw_align_partitions(mi355sw_handle* h, int32_t count, const mi355sw_partition* partitions,
                              const mi355sw_manager* const* managers, void* const* users);
 

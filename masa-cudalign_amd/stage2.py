@@ -203,8 +203,8 @@ class _Speculation:
             self.made = len(self.sweeps)
             if len(jobs) > 1 and hasattr(mgr.aligner, "alignPartitions"):
                 # tall strips: a batch of sweeps that run to their goals hundreds of thousands of rows down is throughput-bound
-                # (1024-row strips: 4.6 TCUPS against the 2.7 of the 256-row strips stage 3's small partitions get), and 1024
-                # keeps the rows this stage stores for stage 3 on CUDAlign's 8192-row grid like the chain's 512
+                # (1024-row strips: 4.6 TCUPS against the 2.7 of the 256-row strips stage 3's small partitions get); on an
+                # aligner at engine-picked heights the batch saves its rows on the chain's 2048-row grid whatever its height
                 kw = {"rows_per_lane": 16} if 16 in getattr(mgr.aligner, "batch_rows_per_lane_choices", ()) else {}
                 mgr.aligner.alignPartitions([a for _, a in jobs], [m for m, _ in jobs], **kw)
             else:
@@ -285,16 +285,17 @@ def stage2(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, sra_limit=0, 
     partitions = 0
     crossing = True
     # Stage 2's partitions are tall and stopped by their goal a few hundred thousand rows down: what they cost is the
-    # first strip's sweep plus one hop per strip down to the goal row, and 512-row strips halve that against the 2048-row
-    # strips the engine's cost model picks for a full sweep of such a shape (mi355sw_set_rows_per_lane).  Only when the
-    # caller left the height to the engine.
+    # first strip's sweep plus one hop per strip down to the goal row, and short strips halve that against the 2048-row
+    # strips the engine's cost model picks for a full sweep of such a shape.  The engine recognises such a sweep by its
+    # shape and picks 512- or 256-row strips for it itself (AlignJob::begin), as its own choice: the special rows stay on
+    # the 2048-row grid of every height the engine picks -- the grid the batched sweeps from guessed crosspoints
+    # (_Speculation) save theirs on too.  (Until the batch followed its parent's grid this loop pinned 512-row strips with
+    # mi355sw_set_rows_per_lane: its rows then lay on the 512-row grid, the batch's on the 1024-row one, and for a spacing
+    # above 8192 that the two round differently an accepted sweep left other rows than the chain's.)
     # (Round 4 tried heights that follow the partition's width -- the goal lies about as many rows down as the partition is
     #  wide, and the strips of a second round of wavefronts come a whole sweep late.  C3, 700 k-column partitions: 768-row
     #  strips 13.1 s against 14.8 s, but the special rows this stage stores for stage 3 then leave CUDAlign's 8192-row grid
     #  and stage 3 picks another, equally optimal alignment; 1024-row strips, which keep the grid, were slower: 16.8 s.)
-    short_strips = hasattr(aligner, "setRowsPerLane") and aligner.getRowsPerLane() == 0
-    if short_strips:
-        aligner.setRowsPerLane(8)
     try:
         while crossing and part1 is not None:
             col_reader, row_reader = part1.first_column_reader, part1.first_row_reader
@@ -349,7 +350,5 @@ def stage2(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, sra_limit=0, 
                 out.write(cp)
     finally:
         out.close()
-        if short_strips:
-            aligner.setRowsPerLane(0)
     return {"crosspoints": out.tuples(), "end": cp_r.astuple(), "partitions": partitions, "seconds": time.time() - t_start,
             "speculation": guessed if speculate else None}
