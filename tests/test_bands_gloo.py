@@ -7,6 +7,7 @@ import sys
 
 import numpy as np
 import pytest
+from helpers import assert_pruned_cells
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -564,6 +565,11 @@ def test_bands_prune_with_the_chain_wide_best_and_keep_special_rows(pkg, oracle,
                     assert tuple(res[r][mode]["rows"][dp][0]) == (int(row[lim[r], 0]), -oracle.INF), (dp, r)
             else:
                 assert np.all(got[:, 0] <= row[1:, 0]) and got[:, 0].max() == row[1:, 0].max(), dp
+                # the same statement as the GPU suite's: every cell of the row, H and F, exact wherever the reference's rule
+                # could not have skipped it
+                n_must, _ = assert_pruned_cells(got, row[1:], dp, np.arange(1, n + 1), m, n, ref["best"][2], oracle.SMITH_WATERMAN,
+                                                where="%s row %d" % (transport, dp))
+                assert n_must > 0 or dp > ref["best"][0]
     assert all(res[r]["plain"]["pruned"] == 0 for r in range(world))
     assert all(res[r]["pruned"]["pruned"] > 0 for r in range(1, world))
     shared = sum(res[r]["pruned"]["pruned"] for r in range(world))

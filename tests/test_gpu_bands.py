@@ -7,6 +7,7 @@ import os
 import sys
 
 import pytest
+from helpers import SMITH_WATERMAN, assert_pruned_cells, oracle_full
 import torch.multiprocessing as mp
 
 from test_bands_gloo import _free_port
@@ -172,12 +173,12 @@ def _worker_prune(rank, world, port, m, n, q):
             runner = BandRunner(al, dist=dist, rank=rank, world=world, device=None, segment_rows=2048, transport=transport,
                                 prune_blocks=(mode != "plain"))
             rows = {}
-            best = runner.run(m, lim[rank], lim[rank + 1], special_row_interval=8192, n_total=n,
+            best = runner.run(m, lim[rank], lim[rank + 1], special_row_interval=8192, n_total=n, keep_inbound=True,
                               special_row_sink=lambda dp, c0, cells: rows.__setitem__(dp, (c0.copy(), cells.copy())))
             st = al.getStatistics()
             out[mode] = dict(best=tuple(runner.reduce_best(best)), rows=rows, pruned=int(st["pruned_cells"]),
                              cells=int(st["cells"]), hints=runner.hints, special=list(runner.special_rows),
-                             restarts=runner.restarts, kernel=st["profile_kernel"])
+                             restarts=runner.restarts, kernel=st["profile_kernel"], inbound=runner.inbound_column)
             dist.barrier()
             al.close()
         q.put((rank, out))
@@ -224,6 +225,18 @@ def test_chain_of_bands_prunes_with_the_shared_best_and_keeps_special_rows(pkg, 
         for mode in ("pruned", "pruned_host"):
             got = np.concatenate([res[r][mode]["rows"][dp][1] for r in range(world)])
             assert np.all(got[:, 0] <= row[1:, 0]) and got[:, 0].max() == row[1:, 0].max(), (mode, dp)
+            # every cell of the row (the bands' slices side by side: global columns 1 ... n), H and F
+            n_must, _ = assert_pruned_cells(got, row[1:], dp, np.arange(1, n + 1), m, n, ref["best"][2], oracle.SMITH_WATERMAN, where="%s row %d" % (mode, dp))
+            assert n_must > 0 or dp > ref["best"][0], (mode, dp)
+    # the hand-over itself: the boundary column band r received (column lim[r] of the whole matrix, (H, E) of rows 0 ... m) against
+    # the oracle's last column of the matrix cut at lim[r] -- exact without pruning, held to the same rule with it
+    for r in range(1, world):
+        col = oracle_full(oracle, s0, s1[:lim[r]], special_row_interval=0)["last_col"]
+        assert np.array_equal(res[r]["plain"]["inbound"], col), r
+        for mode in ("pruned", "pruned_host"):
+            n_must, _ = assert_pruned_cells(res[r][mode]["inbound"], col, np.arange(0, m + 1), lim[r], m, n, ref["best"][2], oracle.SMITH_WATERMAN,
+                                            where="%s boundary column %d" % (mode, lim[r]))
+            assert n_must > 0 or lim[r] > ref["best"][1], (mode, r)
     # every band stayed on the packed kernel: a boundary column deep inside a long alignment (scores far above the
     # 16-bit range, relative to a window that follows them) is not an overflow
     for mode in ("plain", "pruned", "pruned_host"):
@@ -349,11 +362,11 @@ def _worker_wide(rank, world, port, m, n, q):
             runner = BandRunner(al, dist=dist, rank=rank, world=world, device=None, segment_rows=8192, transport="p2p",
                                 prune_blocks=(mode == "pruned"))
             rows = {}
-            best = runner.run(m, lim[rank], lim[rank + 1], special_row_interval=32768, n_total=n,
+            best = runner.run(m, lim[rank], lim[rank + 1], special_row_interval=32768, n_total=n, keep_inbound=True,
                               special_row_sink=lambda dp, c0, cells: rows.__setitem__(dp, (c0.copy(), cells.copy())))
             st = al.getStatistics()
             out[mode] = dict(best=tuple(runner.reduce_best(best)), rows=rows, pruned=int(st["pruned_cells"]), cells=int(st["cells"]),
-                             restarts=runner.restarts, kernel=st["profile_kernel"])
+                             restarts=runner.restarts, kernel=st["profile_kernel"], inbound=runner.inbound_column)
             dist.barrier()
             al.close()
         q.put((rank, out))
@@ -362,13 +375,17 @@ def _worker_wide(rank, world, port, m, n, q):
 
 
 @pytest.mark.timeout(900)
-def test_wide_bands_with_pruning_against_the_single_partition(pkg):
+def test_wide_bands_with_pruning_against_the_single_partition(pkg, oracle):
     """Two bands of 120 000 columns (two processes, column port between them) -- wide enough for the packed kernel's
     hot chunk loop and for runs of pruned slabs taken 16 at a time, with a first column that arrives through the port --
     against ONE partition on the int32 kernels: same best cell; unpruned, the concatenated special-row slices are the single
-    partition's rows cell for cell; pruned, lower bounds of them (H and F)."""
+    partition's rows cell for cell; pruned, lower bounds of them (H and F).  And against the ORACLE (3.6 * 10^10 cells of oracle_full,
+    half of that again for the seam): the single partition's rows and column n / 2 are the oracle's, the pruned chain's rows and
+    the boundary column its port carried are held to the reference's skip rule (helpers.assert_pruned_cells)."""
     import numpy as np
+    from masa_cudalign_amd.bands import band_limits
     m, n, world = 150000, 240000, 2
+    assert band_limits(n, [1] * world) == [0, n // 2, n]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -389,9 +406,20 @@ def test_wide_bands_with_pruning_against_the_single_partition(pkg):
         i, j, sc = mg.getBestScore()
         want = (i - 1, j - 1, sc)                         # the band runner reports the 0-based cell
         single = {dp: mg.specialRow(dp) for dp in sorted(mg.special_rows) if dp < m}
+        half = n // 2                                     # (band_limits(n, [1, 1]): the column the port carried)
+        part = pkg.Partition(0, 0, m, half)
+        mg = pkg.Stage1Manager(part, keep_last_column=True)
+        al.alignPartition(part, mg)
+        boundary = mg.lastColumn()
     finally:
         al.close()
     assert len(single) >= 3 and want[2] > 50000
+    ref = oracle_full(oracle, s0, s1, special_row_interval=32768)
+    assert (want[0] + 1, want[1] + 1, want[2]) == tuple(ref["best"])
+    ref_rows = dict(zip(ref["special_row_ids"], ref["special_rows"]))
+    assert all(np.array_equal(single[dp], ref_rows[dp]) for dp in single)
+    ref_boundary = oracle_full(oracle, s0, s1[:half], special_row_interval=0)["last_col"]
+    assert np.array_equal(boundary, ref_boundary)
     for mode in ("plain", "pruned"):
         assert all(res[r][mode]["best"] == want for r in range(world)), (mode, [res[r][mode]["best"] for r in range(world)], want)
         assert all(res[r][mode]["restarts"] == 0 and res[r][mode]["kernel"] == 2 for r in range(world)), mode
@@ -401,6 +429,14 @@ def test_wide_bands_with_pruning_against_the_single_partition(pkg):
                 assert np.array_equal(got, row[1:]), dp
             else:
                 assert np.all(got <= row[1:]), dp
+                n_must, _ = assert_pruned_cells(got, ref_rows[dp][1:], dp, np.arange(1, n + 1), m, n, want[2], SMITH_WATERMAN, where="row %d" % dp)
+                assert n_must > 0 or dp > want[0] + 1, dp
+        # the boundary column band 1 received through the port against the oracle's column n / 2
+        if mode == "plain":
+            assert np.array_equal(res[1][mode]["inbound"], ref_boundary)
+        else:
+            n_must, _ = assert_pruned_cells(res[1][mode]["inbound"], ref_boundary, np.arange(0, m + 1), half, m, n, want[2], SMITH_WATERMAN, where="boundary column")
+            assert n_must > 0 or half > want[1] + 1
     assert all(res[r]["plain"]["pruned"] == 0 for r in range(world))
     assert sum(res[r]["pruned"]["pruned"] for r in range(world)) > 0.15 * m * n
 

@@ -6,6 +6,7 @@ Reference: the bound a node starts from is what it knows when it starts -- the b
 itself: AbstractBlockPruning::isBlockPrunable, AbstractBlockPruning.cpp:70-111; canonical best: BestScoreList.cpp:129-195."""
 import numpy as np
 import pytest
+from helpers import assert_pruned_borders, assert_pruned_cells, oracle_full
 
 pytestmark = pytest.mark.gpu
 INF = 999999999
@@ -65,7 +66,6 @@ def test_seed_bound_then_pruned_local_run_against_the_oracle(pkg, oracle, kind):
     from masa_cudalign_amd.engine import SMITH_WATERMAN
     s0, s1 = _pairs(pkg, kind)
     m, n = len(s0), len(s1)
-    from helpers import oracle_full
     ref = oracle_full(oracle, s0, s1)
     want_rows = dict(zip(ref["special_row_ids"], ref["special_rows"]))
     opt = ref["best"][2]
@@ -94,6 +94,9 @@ def test_seed_bound_then_pruned_local_run_against_the_oracle(pkg, oracle, kind):
                 assert np.all(cells <= w), i
                 if i <= ref["best"][0]:                        # the row's maximum lies on the optimal path: exact
                     assert int(cells[:, 0].max()) == int(w[:, 0].max()) and int(cells[:, 0].argmax()) == int(w[:, 0].argmax()), i
+            # every cell handed out, H and the gap component: exact wherever the reference's rule could not have skipped it
+            assert_pruned_borders(got["rows"], got["last_row"], got["last_col"], ref, m, n, opt, SMITH_WATERMAN, col0=False,
+                                  must_rows_upto=ref["best"][0], where="%s bound %d" % (kind, bound))
     finally:
         al.close()
 
@@ -148,6 +151,7 @@ def test_seed_bound_global_then_pruned_run_against_the_oracle(pkg, oracle):
         x = ref["last_col"][1:, 0].astype(np.int64)
         must = _reach(x, np.arange(1, m + 1), n, m, n) >= final
         assert must.any() and np.array_equal(lc[must, 0], ref["last_col"][1:][must, 0])
+        assert assert_pruned_borders(got["rows"], lr, lc, ref, m, n, final, NEEDLEMAN_WUNSCH, col0=False, must_rows_upto=m, where="global seed") > 0
     finally:
         al.close()
 
@@ -246,6 +250,7 @@ def test_a_co_optimal_path_that_can_only_tie_survives_pruning(pkg, oracle):
                     al.close()
                 assert int(lr[-1, 0]) == want, (R, flags, track, lr[-1], want)
                 assert np.all(lr <= ref["last_row"][1:]) and st["pruned_cells"] > 0.3 * M * N
+                assert_pruned_cells(lr, ref["last_row"][1:], M, np.arange(1, N + 1), M, N, want, SMITH_WATERMAN, where="R %d flags %d track %d" % (R, flags, track))
                 if track:
                     assert (best[0] + 1, best[1] + 1, best[2]) == tuple(ref["best"])
 

@@ -5,9 +5,12 @@ slabs go depends on when a wavefront looked at it -- the best cell never does, t
 In this mode a strip tests against the bound as it stood a fixed number of strips above it plus its own finds
 (KernelArgs::det_prefix): two runs leave the same bytes."""
 import hashlib
+from functools import reduce
+from math import gcd
 
 import numpy as np
 import pytest
+from helpers import assert_pruned_borders, engine_ref, oracle_full
 
 from test_gpu_bound import _stream
 
@@ -28,7 +31,7 @@ def _digest(res):
     ("local", 400000, 380000, 4),          # 1563 strips of 256 rows
     ("global", 1500000, 1460000, 8),       # a running LOWER bound of H[m][n]
 ])
-def test_two_runs_leave_the_same_special_rows(pkg, kind, m, n, R):
+def test_two_runs_leave_the_same_special_rows(pkg, oracle, kind, m, n, R):
     from masa_cudalign_amd.engine import SMITH_WATERMAN, NEEDLEMAN_WUNSCH, F_DETERMINISTIC_PRUNE
     s0, s1 = pkg.seqgen.related_pair(m, n, cfg=611)
     rec = SMITH_WATERMAN if kind == "local" else NEEDLEMAN_WUNSCH
@@ -60,6 +63,20 @@ def test_two_runs_leave_the_same_special_rows(pkg, kind, m, n, R):
     for dp in plain["rows"]:
         assert np.all(a["rows"][dp] <= plain["rows"][dp]), dp
     assert np.all(a["last_row"] <= plain["last_row"]) and np.all(a["last_col"] <= plain["last_col"])
+    # ... and exact wherever the reference's rule could not have skipped a cell, H and the gap component, in the reproducible mode
+    # and with the running best alike (helpers.assert_pruned_cells).  The 400 000 x 380 000 case against the unpruned ORACLE
+    # (1.5 * 10^11 cells); the other two against the engine's own unpruned run -- 6 * 10^12 and 2.2 * 10^12 cells are 20 and 7
+    # minutes of the oracle on 16 cores
+    if m * n < 2e11:
+        step = reduce(gcd, sorted(plain["rows"]))
+        want = oracle_full(oracle, s0, s1, special_row_interval=step, block_h=gcd(step, 1024))
+        assert plain["best"] == tuple(want["best"])
+    else:
+        want = engine_ref(plain["rows"], plain["last_row"], plain["last_col"], col0=False)
+    goal = plain["best"][2] if kind == "local" else int(plain["last_row"][-1, 0])
+    for name, run in (("reproducible", a), ("running best", free)):
+        assert assert_pruned_borders(run["rows"], run["last_row"], run["last_col"], want, m, n, goal, rec, col0=False,
+                                     must_rows_upto=plain["best"][0] if kind == "local" else m, where=name) > 0
     # the price: the bound reaches a strip one round of wavefronts later than it could
     print("%s %d x %d: pruned %.3f (reproducible) / %.3f (running best), kernel %.1f / %.1f ms" % (
         kind, m, n, a["stats"]["pruned_cells"] / float(m) / n, free["stats"]["pruned_cells"] / float(m) / n,

@@ -6,6 +6,7 @@ to hand over to the general one mid-way (exact replay, new maximum / window shif
 no such loop) at sizes the oracle cannot sweep."""
 import numpy as np
 import pytest
+from helpers import SMITH_WATERMAN, assert_pruned_borders, oracle_full
 
 pytestmark = pytest.mark.gpu
 EDGE = {0: "AT_ANYWHERE", 1: "AT_SEQUENCE_1", 2: "AT_SEQUENCE_2", 3: "AT_SEQUENCE_1_OR_2", 4: "AT_SEQUENCE_1_AND_2"}
@@ -74,12 +75,14 @@ def test_wide_partitions_against_the_oracle(pkg, oracle, kind, start, end, R):
 
 
 @pytest.mark.parametrize("prune", [False, True])
-def test_hot_loop_and_int32_kernels_agree_on_a_large_related_pair(pkg, prune):
+def test_hot_loop_and_int32_kernels_agree_on_a_large_related_pair(pkg, oracle, prune):
     """300 000 x 200 000 related pair (score ~ 170 000: several window shifts, a ridge of 200 000 columns in exact mode;
     with pruning about a third of the slabs skipped, most of them in runs that are tested and written out eight at a
     time): the packed kernels with their hot loop and the int32 kernels give the same best cell; unpruned also the same
     special rows, last row and last column, cell for cell; pruned, every row is a lower bound of the unpruned one, with
-    the same maximum where the alignment crosses it."""
+    the same maximum where the alignment crosses it -- and every cell, H and the gap component, is held to the reference's
+    skip rule against the unpruned ORACLE (helpers.assert_pruned_cells; 6 * 10^10 cells of oracle_full), so that an error
+    the two kernel families share does not pass."""
     m, n = 300000, 200000
     s0, s1 = pkg.seqgen.related_pair(m, n, cfg=71)
     part = pkg.Partition(0, 0, m, n)
@@ -108,6 +111,10 @@ def test_hot_loop_and_int32_kernels_agree_on_a_large_related_pair(pkg, prune):
             assert np.all(a <= b), i
             if i <= res[2][0][0]:                               # the alignment's ridge crosses this row: its cell survives
                 assert a.max() == b.max(), i
+        ref = oracle_full(oracle, s0, s1, special_row_interval=65536)
+        assert res[0][0] == tuple(ref["best"])
+        assert assert_pruned_borders(res[0][4], res[0][1], res[0][2], ref, m, n, ref["best"][2], SMITH_WATERMAN, col0=True,
+                                     must_rows_upto=ref["best"][0], where="packed pruned / oracle") > 0
     else:
         assert np.array_equal(res[0][1], res[2][1])
         assert np.array_equal(res[0][2], res[2][2])
@@ -191,11 +198,13 @@ def _fuzz_wide(k):
 
 
 @pytest.mark.parametrize("k", range(96))
-def test_randomised_wide_runs_against_the_int32_kernels(pkg, k):
+def test_randomised_wide_runs_against_the_int32_kernels(pkg, oracle, k):
     """96 seeded wide configurations (20 000-220 000 rows x 40 000-320 000 columns, related pairs with 1-20 % substitutions,
     runs of N, every strip height; local with and without pruning, global, semi-global; with and without special rows):
     the packed kernels (hot chunk loop, runs of pruned slabs) against the int32 kernels, which have neither -- same best
-    cell; without pruning the same last row, last column and special rows, cell for cell; with pruning lower bounds."""
+    cell; without pruning the same last row, last column and special rows, cell for cell; with pruning lower bounds of the int32
+    run's cells, and every cell held to the reference's skip rule against the unpruned ORACLE (37 of the 96 shapes prune: 10^12
+    cells of oracle_full in all, the largest 6.6 * 10^10)."""
     m, n, s0, s1, R, mode, interval = _fuzz_wide(k)
     start, end = {"sw": (0, 0), "sw_prune": (0, 0), "nw": (4, 4), "semi": (1, 3)}[mode]
     part = pkg.Partition(0, 0, m, n)
@@ -224,6 +233,10 @@ def test_randomised_wide_runs_against_the_int32_kernels(pkg, k):
         assert np.all(res[0][1] <= res[2][1]) and np.all(res[0][2] <= res[2][2])
         for i in res[0][4]:
             assert np.all(res[0][4][i] <= res[2][4][i]), i
+        ref = oracle_full(oracle, s0, s1, special_row_interval=interval)
+        assert res[0][0] == tuple(ref["best"])
+        assert_pruned_borders(res[0][4], res[0][1], res[0][2], ref, m, n, ref["best"][2], SMITH_WATERMAN, col0=True,
+                              must_rows_upto=ref["best"][0], where="wide %d" % k)
     else:
         assert np.array_equal(res[0][1], res[2][1]) and np.array_equal(res[0][2], res[2][2])
         for i in res[0][4]:

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from helpers import load_golden, make_pair, digest, parse_args, flush_interval
+from helpers import assert_pruned_borders, manager_rows
 
 pytestmark = pytest.mark.gpu
 G = load_golden()
@@ -406,6 +407,10 @@ def test_block_pruning_keeps_the_canonical_best(pkg, oracle):
                 assert got.max() == want.max() and int(got.argmax()) == int(want.argmax())
                 crossed += 1
         assert crossed >= 4
+        # every cell of every row, H and F, above AND below the best cell: exact wherever the reference's own rule could not
+        # have skipped it (helpers.assert_pruned_cells) -- which is also the statement of what the rows below the best cell owe
+        assert assert_pruned_borders(manager_rows(mgp), None, None, ref, m, n, ref["best"][2], oracle.SMITH_WATERMAN, col0=True,
+                                     must_rows_upto=ref["best"][0], where="pruned") > 10000
     finally:
         al.close()
 
@@ -471,6 +476,8 @@ def test_randomised_differential_against_oracle(pkg, oracle, k):
         if not (prune and st["pruned_cells"] > 0):
             assert np.array_equal(mg.lastRow(), ref["last_row"])
             assert np.array_equal(mg.lastColumn(), ref["last_col"])
+        else:                                                 # a run that did prune: lower bounds, exact where they can matter
+            assert_pruned_borders({}, mg.lastRow(), mg.lastColumn(), ref, m, n, ref["best"][2], oracle.SMITH_WATERMAN, col0=True, where="fuzz %d" % k)
     finally:
         al.close()
 

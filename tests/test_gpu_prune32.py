@@ -3,6 +3,7 @@ byte values common to both sequences: IUPAC-rich FASTA), MI355SW_F_FORCE_INT32 a
 Reference: the reference prunes in every instantiation of its kernels (X/CUDAligner.cu:950-960, AbstractBlockPruning.cpp:70-111)."""
 import numpy as np
 import pytest
+from helpers import assert_pruned_borders, assert_pruned_cells, manager_rows, oracle_full
 
 pytestmark = pytest.mark.gpu
 IUPAC = np.frombuffer(b"ACGTNRYKMSWBDHV", dtype=np.uint8)          # 15 letters: one too many for the packed kernel's profile
@@ -22,7 +23,6 @@ def _iupac_pair(pkg, m, n, cfg):
 
 @pytest.mark.parametrize("mode", ["iupac", "forced"])
 def test_int32_family_prunes_and_keeps_the_oracles_best(pkg, oracle, mode):
-    from helpers import oracle_full
     from masa_cudalign_amd.engine import F_FORCE_INT32
     m, n = 60000, 50000
     if mode == "iupac":
@@ -59,6 +59,9 @@ def test_int32_family_prunes_and_keeps_the_oracles_best(pkg, oracle, mode):
                 assert np.all(got <= want) and np.all(got[1:, 0] >= 0), i
                 if i <= ref["best"][0]:
                     assert got[:, 0].max() == want[:, 0].max() and got[:, 0].argmax() == want[:, 0].argmax(), i
+            # the int32 family's skip test is held to the same rule as the packed kernel's: every cell, H and the gap component
+            assert assert_pruned_borders(manager_rows(mgp), mgp.lastRow(), mgp.lastColumn(), ref, m, n, ref["best"][2], oracle.SMITH_WATERMAN,
+                                         col0=True, must_rows_upto=ref["best"][0], where="%s R %d" % (mode, R)) > 0
         finally:
             al.close()
 
@@ -91,5 +94,6 @@ def test_int32_pruning_with_an_initial_bound_and_the_tie_path(pkg, oracle):
                 st = al.getStatistics()
                 assert (best[0] + 1, best[1] + 1, best[2]) == tuple(ref["best"]), (R, bound)
                 assert int(lr[-1, 0]) == want and np.all(lr <= ref["last_row"][1:]) and st["pruned_cells"] > 0.3 * M * N, (R, bound)
+                assert_pruned_cells(lr, ref["last_row"][1:], M, np.arange(1, N + 1), M, N, want, oracle.SMITH_WATERMAN, where="R %d bound %s" % (R, bound))
         finally:
             al.close()

@@ -14,6 +14,7 @@ import pytest
 import torch.multiprocessing as mp
 
 from test_bands_gloo import _free_port
+from helpers import NEEDLEMAN_WUNSCH, SMITH_WATERMAN, assert_pruned_borders, assert_pruned_cells, engine_ref, manager_rows, oracle_full
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,6 +51,8 @@ def _check_lower_bounds(mg, ref, m, n, final):
         assert np.all(got <= want), i
         must = _reach(want[:, 0].astype(np.int64), i, np.arange(0, n + 1), m, n) >= final
         assert must.any() and np.array_equal(got[must, 0], want[must, 0]), i
+    # the same on every cell through the one statement of the suite, H and the gap component
+    assert assert_pruned_borders(manager_rows(mg), lr, lc, ref, m, n, final, NEEDLEMAN_WUNSCH, col0=True, must_rows_upto=m, where="global") > 0
 
 
 def test_global_pruning_against_the_oracle(pkg, oracle):
@@ -205,6 +208,7 @@ def test_chain_of_bands_prunes_a_global_alignment(pkg, oracle):
             assert np.array_equal(row, ref["last_row"][1:])
         else:
             assert np.all(row <= ref["last_row"][1:])
+            assert assert_pruned_cells(row, ref["last_row"][1:], m, np.arange(1, n + 1), m, n, final, NEEDLEMAN_WUNSCH, where=mode + " last row")[0] > 0
         for dp in sorted(want_rows):
             if dp >= m:
                 continue
@@ -216,6 +220,7 @@ def test_chain_of_bands_prunes_a_global_alignment(pkg, oracle):
                 assert np.all(got <= want), (mode, dp)
                 must = _reach(want[:, 0].astype(np.int64), dp, np.arange(1, n + 1), m, n) >= final
                 assert must.any() and np.array_equal(got[must, 0], want[must, 0]), (mode, dp)
+                assert assert_pruned_cells(got, want, dp, np.arange(1, n + 1), m, n, final, NEEDLEMAN_WUNSCH, where="%s row %d" % (mode, dp))[0] > 0
     assert all(res[r]["plain"]["pruned"] == 0 for r in range(world))
     for mode in ("pruned", "pruned_host"):
         assert sum(res[r][mode]["pruned"] for r in range(world)) > 0.25 * m * n, mode
@@ -225,11 +230,13 @@ def test_chain_of_bands_prunes_a_global_alignment(pkg, oracle):
         ["%.2f" % (res[r]["pruned_host"]["pruned"] / res[r]["pruned_host"]["cells"]) for r in range(world)]))
 
 
-def test_local_pruning_far_above_the_16_bit_window(pkg):
+def test_local_pruning_far_above_the_16_bit_window(pkg, oracle):
     """400 000 x 300 000 related pair, scores up to 236 000: slabs whose entering scores are hundreds of thousands are
     skipped like any other (round 3 only skipped below 16 000 with the window at the floor).  Best cell = the int32
     kernels' (no pruning there); special rows, last row and last column are lower bounds with the row maximum intact
-    above the best cell; more than 45 % of the matrix skipped; the packed kernel never hands over to the int32 ones."""
+    above the best cell; more than 45 % of the matrix skipped; the packed kernel never hands over to the int32 ones.  Every cell
+    handed out, H and the gap component, is held to the reference's skip rule against the unpruned ORACLE (1.2 * 10^11 cells of
+    oracle_full), which also vouches for the int32 run's best cell."""
     m, n = 400000, 300000
     s0, s1 = pkg.seqgen.related_pair(m, n, cfg=41)
     part = pkg.Partition(0, 0, m, n)
@@ -254,6 +261,10 @@ def test_local_pruning_far_above_the_16_bit_window(pkg):
         assert np.all(y <= x) and np.all(y[1:, 0] >= 0), i
         if i <= a.getBestScore()[0]:
             assert y[:, 0].max() == x[:, 0].max() and int(y[:, 0].argmax()) == int(x[:, 0].argmax()), i
+    ref = oracle_full(oracle, s0, s1, special_row_interval=49152)
+    assert tuple(a.getBestScore()) == tuple(ref["best"])
+    assert assert_pruned_borders(manager_rows(b), b.lastRow(), b.lastColumn(), ref, m, n, ref["best"][2], SMITH_WATERMAN, col0=True,
+                                 must_rows_upto=ref["best"][0], where="far above the window") > 0
 
 
 def test_diagonal_seed_gives_the_same_answers_and_prunes_more(pkg, monkeypatch):
@@ -261,7 +272,9 @@ def test_diagonal_seed_gives_the_same_answers_and_prunes_more(pkg, monkeypatch):
     diagonal (runtime.cpp::diagonal_seed; the reference seeds its bound with the best of a resumed run or of the other
     nodes, sw_stage1.cpp:210-217, AlignerPool).  The seed is the score of a real alignment, so nothing may change but the
     amount of work: same best cell (local) / same H[m][n] (global) as without the seed and as without pruning, special
-    rows lower bounds of the unpruned ones with the row maxima intact above the best cell, more cells skipped."""
+    rows lower bounds of the unpruned ones with the row maxima intact above the best cell, more cells skipped.  The cell check
+    (helpers.assert_pruned_cells) is engine against engine here -- the unpruned run of the same kernels is its `want`: 7.65 * 10^13
+    cells are four to five hours of the oracle on 16 cores."""
     m, n = 9000000, 8500000                      # (the seed only runs from 8 Mi x 8 Mi: below that it costs more than it saves)
     s0, s1 = pkg.seqgen.related_pair(m, n, cfg=37)
     part = pkg.Partition(0, 0, m, n)
@@ -295,6 +308,10 @@ def test_diagonal_seed_gives_the_same_answers_and_prunes_more(pkg, monkeypatch):
                 if edge != pkg.AT_ANYWHERE:
                     must = _reach(x[:, 0].astype(np.int64), i, np.arange(0, n + 1), m, n) >= a.getBestScore()[2]
                     assert must.any() and np.array_equal(y[must, 0], x[must, 0]), i
+            for name, run in (("no seed", b), ("seeded", c)):
+                assert assert_pruned_borders(manager_rows(run), None, None, engine_ref(manager_rows(a), None, None, col0=True), m, n, a.getBestScore()[2],
+                                             pkg.SMITH_WATERMAN if edge == pkg.AT_ANYWHERE else pkg.NEEDLEMAN_WUNSCH, col0=True,
+                                             must_rows_upto=best_row if edge == pkg.AT_ANYWHERE else m, where="%s edge %d" % (name, edge)) > 0
             print("edge %d: skipped %.3f without the seed, %.3f with it (seed %.0f ms); kernel %.0f -> %.0f ms" % (
                 edge, sb["pruned_cells"] / float(m) / n, sc["pruned_cells"] / float(m) / n, sc["seed_ms"], sb["kernel_ms"], sc["kernel_ms"]))
     finally:

@@ -7,6 +7,7 @@ Reference: BlockPruningDiagonal::updatePruningWindow (M/libmasa/pruning/BlockPru
 the same run without the window (MI355SW_F_NO_WINDOW) and, for every value that matters, the unpruned oracle."""
 import numpy as np
 import pytest
+from helpers import assert_pruned_borders, manager_rows, oracle_full
 
 from test_gpu_bound import _stream
 
@@ -48,7 +49,6 @@ def test_window_against_the_oracle_and_against_the_run_without_it(pkg, oracle, k
     the window the best cell / H[m][n] is the oracle's; last row, last column and every special row are lower bounds of the
     oracle's rows; and the run without the window -- same kernels, every skipped cell written -- agrees on all of it"""
     from masa_cudalign_amd.engine import SMITH_WATERMAN, NEEDLEMAN_WUNSCH, F_NO_WINDOW
-    from helpers import oracle_full
     s0, s1, m, n, R, kind = _pair(pkg, k)
     rec = NEEDLEMAN_WUNSCH if kind == 2 else SMITH_WATERMAN
     edge = 4 if kind == 2 else 0
@@ -84,6 +84,10 @@ def test_window_against_the_oracle_and_against_the_run_without_it(pkg, oracle, k
                 w = want_rows[i][1:, 0]
                 if i <= ref["best"][0] and int(w.max()) > 200:
                     assert int(cells[:, 0].max()) == int(w.max()) and int(cells[:, 0].argmax()) == int(w.argmax()), (flags, i)
+        # every cell handed out, H and the gap component (the stream's rows have no column 0): exact wherever the reference's
+        # rule could not have skipped it; a row the optimal alignment crosses always has such cells
+        assert_pruned_borders(got["rows"], got["last_row"], got["last_col"], ref, m, n, final if kind == 2 else ref["best"][2], rec,
+                              col0=False, must_rows_upto=m if kind == 2 else ref["best"][0], where="k %d flags %d" % (k, flags))
     a, b = res[0], res[F_NO_WINDOW]
     # the window changes what is WRITTEN, not what is skipped (up to the timing of the running bound, which may differ by a few slabs)
     assert abs(a["stats"]["pruned_cells"] - b["stats"]["pruned_cells"]) <= 0.05 * m * n, (a["stats"]["pruned_cells"], b["stats"]["pruned_cells"])
@@ -157,5 +161,7 @@ def test_window_through_the_manager_interface_with_pruning_on(pkg, oracle):
                 assert got[:, 0].max() == want[:, 0].max() and got[:, 0].argmax() == want[:, 0].argmax(), i
                 crossed += 1
         assert crossed >= 5
+        assert assert_pruned_borders(manager_rows(mg), mg.lastRow(), mg.lastColumn(), ref, m, n, ref["best"][2], oracle.SMITH_WATERMAN, col0=True,
+                                     must_rows_upto=ref["best"][0], where="manager") > 0
     finally:
         al.close()
