@@ -28,7 +28,7 @@ class OracleStreamEngine:
         self._opts.update(kw)
 
     # -- column ports, stood in by POSIX shared memory between the rank processes: int32 row counter at +0, cells from
-    #    +256 -- the layout of the engine's port (csrc/runtime.cpp); the "kernel" below publishes and polls like
+    #    +256 -- the layout of the engine's port (csrc/runtime_layout.h); the "kernel" below publishes and polls like
     #    complete_strip_common / claim_strip_common do
     def portCreate(self, rows):
         from multiprocessing import shared_memory
