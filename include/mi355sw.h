@@ -250,7 +250,7 @@ int mi355sw_align_partition(mi355sw_handle* h, const mi355sw_partition* partitio
  * mi355sw_align_partition(h, &partitions[k], managers[k], users[k]) had been called for every k -- same hooks, same
  * order PER partition, all from the calling thread -- but the partitions run side by side, so the calls of different
  * managers interleave.  Every partition needs its own manager state (borders, goal, sinks).  Partitions the batch
- * cannot take (more than 14 common byte values, >= 32 Mi rows, block pruning or block scores wanted, an overflow report
+ * cannot take (more than 14 common byte values, >= 32 Mi rows, block pruning (other than by goal bounds) or block scores wanted, an overflow report
  * of the packed kernel) are run one by one after the others; an overflow rerun replays what the batch attempt already
  * took and handed over (streamed first-column cells, last-column rows, special rows), as a single call's rerun does.
  * Special rows: the batch's strip height (mi355sw_config.batch_rows_per_lane) is the engine's own choice when the handle's
@@ -260,6 +260,23 @@ int mi355sw_align_partition(mi355sw_handle* h, const mi355sw_partition* partitio
  * mi355sw_get_stats: sums over the call. */
 int mi355sw_align_partitions(mi355sw_handle* h, int32_t count, const mi355sw_partition* partitions,
                              const mi355sw_manager* const* managers, void* const* users);
+
+/* Goal pruning (additive in ABI 8): bounds for the NEXT mi355sw_stream_begin / mi355sw_align_partition (count 1) or
+ * mi355sw_align_partitions (count = its count), consumed by that call.  For a sweep that looks for a GOAL score on its last
+ * column -- stage 2: a global recurrence from a crosspoint, matched there against a special row of stage 1 -- the caller
+ * knows the score it must reach and an upper bound P of the forward values it will be matched against:
+ *   column_bounds[k] = goal - P - gap_open       every last-column cell that can meet the goal holds at least this
+ *   row_bounds[k]    = the same against the border behind the last ROW, when the manager reads one for the goal
+ * -MI355SW_INF: that term is off (row_bounds may be NULL: all off); both off: no bound for that partition.  A slab of cells
+ * is skipped when nothing that enters it can still reach a bound that is on -- value + columns left for the column, value +
+ * min(rows, columns left) - 2 * (rows left - columns left, if positive) for the row.  Skipped cells read -MI355SW_INF, every
+ * other cell is its true value or a lower bound of it, and every cell at or above its bound, with every cell on a path to
+ * it, is exact.  The bounds are constants, so which cells go is a function of the input.  Applies to NEEDLEMAN_WUNSCH partitions
+ * with nothing tracked whose last column is dispatched, on the packed kernels at 256- / 512-row strips (rows_per_lane 4 / 8,
+ * or 0: picked by the engine), in a batch at 256- / 1024-row strips; anything else -- more than 14 byte values,
+ * MI355SW_F_FORCE_INT32, an overflow rerun -- computes every cell.  No probe or seed runs and MI355SW_EBOUND does not apply
+ * (the bound is not the score of a last cell).  mi355sw_stats.pruned_cells / processed_cells / kernel report it. */
+int mi355sw_set_goal_bounds(mi355sw_handle* h, int32_t count, const int32_t* column_bounds, const int32_t* row_bounds);
 
 /* AbstractBlockProcessor::processBlock (M/libmasa/processors/AbstractBlockProcessor.hpp:27-37,
  * semantics CPUBlockProcessor.cpp:95-112): row[k] = (H,F) of (i0-1,j0+k) in/out, col[0] = diagonal

@@ -102,6 +102,13 @@ struct KernelArgs {
     const int* gbest_in;         // where the strips READ the running best from: gbest itself, or a word that stays at -INF
                                  // when every strip record must be that strip's own exact best (block scores) instead
                                  // of "nothing below what is already known elsewhere"
+    // ---- goal pruning (mi355sw_set_goal_bounds; the GOAL instantiations of the packed pruning kernels) ----
+    // A sweep that looks for a goal on its last column (stage 2) skips a slab when nothing that enters it can still reach
+    //   goal_bound_col  on the last column   (upper bound of a path: value + columns left), nor
+    //   goal_bound_row  on the last row      (value + min(rows, columns left) - 2 * (rows left - columns left, if positive)).
+    // T domain like gbest; constants of the sweep, so which slabs go is a function of the input.  -INF: that term is off
+    // (nobody reads that border for the goal).
+    int goal_bound_col = -999999999, goal_bound_row = -999999999;   // (the only members with an initialiser: KernelArgs{} is "no goal")
 };
 
 // The argument block lives in device memory and is read through the constant address space with a
@@ -277,12 +284,14 @@ hipError_t launch_strip_kernel_pk16_mixed(const KernelArgs& a, KernelArgs* dargs
                                           hipStream_t stream, bool track, bool sw);
 hipError_t launch_batch_kernel_pk16(const BatchArgs* dbatch, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw);
 hipError_t launch_batch_kernel_pk16_band(const BatchArgs* dbatch, int grid, hipStream_t stream);   // 512-row strips, NW, value-only, pruning kernels (band mode)
+// goal mode (KernelArgs::goal_bound_col / _row): NW, nothing tracked, pruning kernels; 256- and 1024-row strips (rows_per_half 2, 8)
+hipError_t launch_batch_kernel_pk16_goal(const BatchArgs* dbatch, int rows_per_half, int grid, hipStream_t stream);
 
 // `dargs` = device copy of the argument block (the launcher uploads `a` into it on `stream`)
 hipError_t launch_strip_kernel(const KernelArgs& a, KernelArgs* dargs, int rows_per_lane, int grid, hipStream_t stream,
                                bool sw, bool profile, bool track);
 int strip_kernel_waves_per_simd(int rows_per_lane);   // int32 family: wavefronts of one launch that share a SIMD (2 for 256/512-row strips; the packed kernels: 1)
-// packed 16-bit SW kernel (sw_kernel_pk16.inc, instantiated by sw_kernel_pk16_{a..h}.hip): strip height = 128*rows_per_half
+// packed 16-bit SW kernel (sw_kernel_pk16.inc, instantiated by sw_kernel_pk16_{a..i}.hip): strip height = 128*rows_per_half
 hipError_t launch_strip_kernel_pk16(const KernelArgs& a, KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw);
 // stage 4 (stage4.hip): Myers-Miller refinement of a crosspoint list, batched on the GPU
 struct Stage4Crosspoint { int type, i, j, score; };          // M/common/Crosspoint.hpp

@@ -491,7 +491,22 @@ __device__ __forceinline__ int nw_lower16(const int t, const long long kmax, con
     return lb > (long long) NEG_INF ? (int) lb : NEG_INF;
 }
 
-template <int R, bool TRACK, bool SWF, bool PRUNE>
+// GOAL mode of the global pruning kernels (round 7): the sweep looks for a goal score met somewhere on its LAST COLUMN -- a
+// stage-2 sweep from a crosspoint, matched there against a special row of stage 1 -- and, when its partition runs to the
+// matrix's border, on its last row.  The bounds are constants of the sweep (KernelArgs::goal_bound_col / _row, T domain):
+// a cell that holds t with dj columns left reaches the last column with at most t + dj (every step a match), and the last
+// row with at most t + min(di, dj) - 2 * (di - dj) when it has more rows left than columns (the surplus is a gap).  A slab
+// goes when nothing that enters it stays at or above a bound that is on; the test is strict and keeps NW_PRUNE_MARGIN.
+// `t` bounds cells whose rows-left lie in [di - si, di] and whose columns-left are at most dj.  (64-bit: t + dj need not fit.)
+__device__ __forceinline__ bool goal_keep16(const int t, const int di, const int dj, const int si, const long long gcol, const long long grow) {
+    if (t <= NEG_INF / 2) return false;                   // nothing enters here
+    const long long ucol = (long long) t + dj + NW_PRUNE_MARGIN;
+    const long long surplus = (long long) di - si - dj;   // the least (rows left - columns left) among the cells
+    const long long urow = (long long) t + min(di, dj) - 2 * (surplus > 0 ? surplus : 0) + NW_PRUNE_MARGIN;
+    return ucol >= gcol || urow >= grow;
+}
+
+template <int R, bool TRACK, bool SWF, bool PRUNE, bool GOAL = false>
 __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, const int s_in, WaveLds16* lds, const int lane) {
     const UniformArgs a = uniform_args(ap);
     const int s = __builtin_amdgcn_readfirstlane(s_in);
@@ -660,6 +675,12 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
     const int pr_rows = pin32_16(a->prune_rows - 1 - row0);   // rows of the super-partition below the strip's first row
     const int pr_cols = pin32_16(a->prune_cols - 1);
     int pruned_slabs = 0;
+    static_assert(!GOAL || (PRUNE && !SWF && !TRACK), "goal mode: global recurrence, pruning kernels, nothing tracked");
+    // goal mode: the two bounds, a term that is off (-INF in the argument block) out of every value's reach
+    const int goal_c = GOAL ? pin32_16(a->goal_bound_col) : NEG_INF, goal_r = GOAL ? pin32_16(a->goal_bound_row) : NEG_INF;
+    const long long gcol = goal_c <= NEG_INF / 2 ? 0x7fffffffffffffffll : (long long) goal_c;
+    const long long grow = goal_r <= NEG_INF / 2 ? 0x7fffffffffffffffll : (long long) goal_r;
+    const bool goal_any = goal_c > NEG_INF / 2 || goal_r > NEG_INF / 2;    // (a partition of a batch that brought no bound: nothing goes)
 
     // seq1 window starts empty
     lds->c1w[lane] = 0x00020002; lds->c1w[64 + lane] = 0x00020002; lds->c1w[128 + lane] = 0x00020002;
@@ -688,7 +709,7 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
     const unsigned char* const seq1p = pin_ptr16(a->seq1);
     // reproducible pruning (KernelArgs::det_prefix): the bound this strip tests against is a word that is final before the strip
     // starts -- what the run began with and what the strips det_lag and more above found -- plus what the strip itself finds
-    const bool det = prune_on && a->det_prefix != nullptr;
+    const bool det = prune_on && !GOAL && a->det_prefix != nullptr;
     const int* const gbest_inp = pin_ptr16(det ? (const int*) &a->det_prefix[max(0, s - a->det_lag)] : a->gbest_in);
     if (det) {
         int spins = 0;
@@ -844,6 +865,11 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
                     int e = lane_entry;
                     if (col < n) e = max(e, hf.x - T_OFF);
                     skip = !__any(e + left + SW_PRUNE_MARGIN >= gseen);
+                } else if (GOAL) {
+                    // (the same two entries as below, held against the sweep's own bounds: see goal_keep16)
+                    const bool own = goal_keep16(lane_entry, pr_rows - 2 * lane * R, pr_cols - col0 + 2 * lane + 4, 2 * R - 1, gcol, grow);
+                    const bool top = goal_keep16(col < n ? hf.x - T_OFF : NEG_INF, pr_rows + 1, pr_cols - col + 1, 0, gcol, grow);
+                    skip = goal_any && !__any(own || top);
                 } else {
                     // what enters the slab: the lane's own last column (rows of its two blocks, columns col0 - 2 lane - 4 ..
                     // + 1 with room to spare) and the bus cell of its column (row above the strip)
@@ -1097,7 +1123,7 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
             // global alignments with pruning: what this chunk's cells say about H[m][n] from below.  The lane's maximum is
             // the score of one of its cells -- rows of its two blocks, columns col0 - 2 lane - 1 .. + 63 -- wherever it is.
             int lbv = NEG_INF;
-            if (prune_nw && !skip && !masked && nvalid_lo == R && nvalid_hi == R) {
+            if (prune_nw && !GOAL && !skip && !masked && nvalid_lo == R && nvalid_hi == R) {   // (goal mode: the bound is fixed)
                 const long long ki = (long long) pr_rows - 2 * lane * R, dj = (long long) pr_cols - col0 + 2 * lane + 1;
                 const long long dhi = dj - (ki - (2 * R - 1)), dlo = (dj - 64) - ki;
                 lbv = nw_lower16(cmv + bias, ki < dj ? ki : dj, dhi > -dlo ? dhi : -dlo);
@@ -1129,7 +1155,7 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
                     det_found = max(det_found, news);
                     gb_next = max(gb_next, news);
                 }
-                if ((TRACK || prune_on) && news > gseen) {
+                if ((TRACK || prune_on) && !GOAL && news > gseen) {
                     if (lane == 0) {
                         atomicMax(a->gbest, news);
                         if (prune_on) {     // tell the neighbouring bands at once (they fold it into their own gbest)
@@ -1308,6 +1334,8 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
                         const int left = min(pr_rows + 2, pr_cols + 1 - (col0 + k * CHUNK - 128));
                         const int e = max(lane_entry, h[k] - T_OFF);
                         if (!__any(e + left + SW_PRUNE_MARGIN >= gs)) count = k + 1;
+                    } else if (GOAL) {
+                        if (goal_any && !__any(goal_keep16(h[k] - T_OFF, pr_rows + 1, pr_cols - (col0 + k * CHUNK + lane) + 1, 0, gcol, grow))) count = k + 1;
                     } else {
                         // (the strip holds nothing: only the bus cells can bring a path in)
                         const int top = nw_upper16(h[k] - T_OFF, pr_rows + 1, pr_cols - (col0 + k * CHUNK + lane) + 1, 0, 1);
@@ -1547,7 +1575,7 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
     }
 }
 
-template <int R, bool TRACK, bool SWF, bool PRUNE>
+template <int R, bool TRACK, bool SWF, bool PRUNE, bool GOAL = false>
 __global__ void __launch_bounds__(64) sw_strip_kernel_pk16(const KernelArgs* __restrict__ ap) {
     __shared__ WaveLds16 lds_store;
     WaveLds16* lds = &lds_store;
@@ -1571,7 +1599,7 @@ __global__ void __launch_bounds__(64) sw_strip_kernel_pk16(const KernelArgs* __r
             __builtin_amdgcn_wave_barrier();
             break;
         } else {
-            process_strip16<R, TRACK, SWF, PRUNE>(ap, s, lds, lane);
+            process_strip16<R, TRACK, SWF, PRUNE, GOAL>(ap, s, lds, lane);
         }
         complete_strip_common(ap, s, lane, 128 * R, true);
     }
@@ -1609,7 +1637,7 @@ __global__ void __launch_bounds__(64) sw_strip_kernel_pk16_mixed(const KernelArg
 // Several partitions in one launch (BatchArgs, sw_kernel.h): the same strip function, the argument block of the
 // partition the ticket belongs to.  256- and 512-row strips only: the partitions that come in batches (stage 3's walks
 // between two special rows) are tall, narrow and stopped early -- what they need is many of them in flight.
-template <int R, bool TRACK, bool SWF, bool PRUNE = false>
+template <int R, bool TRACK, bool SWF, bool PRUNE = false, bool GOAL = false>
 __global__ void __launch_bounds__(64) sw_batch_kernel_pk16(const BatchArgs* __restrict__ bp) {
     __shared__ WaveLds16 lds_store;
     WaveLds16* lds = &lds_store;
@@ -1635,14 +1663,14 @@ __global__ void __launch_bounds__(64) sw_batch_kernel_pk16(const BatchArgs* __re
             if (lane == 0) st_agent16(&a->progress[s + 1], a->n);
             __builtin_amdgcn_wave_barrier();
         } else {
-            process_strip16<R, TRACK, SWF, PRUNE>(ap, s, lds, lane);
+            process_strip16<R, TRACK, SWF, PRUNE, GOAL>(ap, s, lds, lane);
         }
         complete_strip_common(ap, s, lane, 128 * R, false);     // (every ticket of a batch goes through here in order)
     }
 }
 
 // One launcher per strip height and pruning mode; they are spread over six translation units
-// (sw_kernel_pk16_{a..f}.hip define PK16_PART) so that the instantiations compile in parallel.
+// (sw_kernel_pk16_{a..i}.hip define PK16_PART) so that the instantiations compile in parallel.
 template <int RV, bool PRUNE>
 hipError_t launch16_r(const KernelArgs* dargs, int grid, hipStream_t stream, bool track, bool sw) {
 #define LAUNCH16(TRV, SWV) hipLaunchKernelGGL((sw_strip_kernel_pk16<RV, TRV, SWV, PRUNE>), dim3(grid), dim3(64), 0, stream, dargs)
@@ -1661,12 +1689,18 @@ PK16_DECL(12, false, extern) PK16_DECL(16, false, extern)
 PK16_DECL(2, true, extern) PK16_DECL(4, true, extern) PK16_DECL(6, true, extern) PK16_DECL(8, true, extern)
 PK16_DECL(12, true, extern) PK16_DECL(16, true, extern)
 
+hipError_t launch_strip_kernel_pk16_goal(const KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream);   // (unit i)
 hipError_t launch_strip_kernel_pk16(const KernelArgs& a, KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw) {
     hipError_t e = hipMemcpyAsync(dargs, &a, sizeof(KernelArgs), hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) return e;
     e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
     const bool pr = a.prune != 0;
+    // goal mode (unit i): the heights a goal sweep runs at
+    if (pr && (a.goal_bound_col > NEG_INF / 2 || a.goal_bound_row > NEG_INF / 2)) {
+        if (track || sw) return hipErrorInvalidValue;
+        return launch_strip_kernel_pk16_goal(dargs, rows_per_half, grid, stream);
+    }
 #define PK16_CASE(RV) case RV: return pr ? launch16_r<RV, true>(dargs, grid, stream, track, sw) : launch16_r<RV, false>(dargs, grid, stream, track, sw);
     switch (rows_per_half) {
     PK16_CASE(2) PK16_CASE(4) PK16_CASE(6) PK16_CASE(8) PK16_CASE(12) PK16_CASE(16)
@@ -1714,6 +1748,21 @@ hipError_t launch_batch_kernel_pk16_r8(const BatchArgs* dbatch, int grid, hipStr
               else hipLaunchKernelGGL((sw_batch_kernel_pk16<8, false, true>), dim3(grid), dim3(64), 0, stream, dbatch); }
     else { if (track) hipLaunchKernelGGL((sw_batch_kernel_pk16<8, true, false>), dim3(grid), dim3(64), 0, stream, dbatch);
            else hipLaunchKernelGGL((sw_batch_kernel_pk16<8, false, false>), dim3(grid), dim3(64), 0, stream, dbatch); }
+    return hipGetLastError();
+}
+#elif PK16_PART == 8
+// goal mode (process_strip16<.., GOAL>): what a goal sweep gets from AlignJob::begin -- 256- and 512-row strips -- and the batches
+// of stage 2's sweeps from guessed crosspoints, 256- and 1024-row strips; global recurrence, nothing tracked, pruning kernels
+hipError_t launch_strip_kernel_pk16_goal(const KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream) {
+    if (rows_per_half == 2) hipLaunchKernelGGL((sw_strip_kernel_pk16<2, false, false, true, true>), dim3(grid), dim3(64), 0, stream, dargs);
+    else if (rows_per_half == 4) hipLaunchKernelGGL((sw_strip_kernel_pk16<4, false, false, true, true>), dim3(grid), dim3(64), 0, stream, dargs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_batch_kernel_pk16_goal(const BatchArgs* dbatch, int rows_per_half, int grid, hipStream_t stream) {
+    if (rows_per_half == 2) hipLaunchKernelGGL((sw_batch_kernel_pk16<2, false, false, true, true>), dim3(grid), dim3(64), 0, stream, dbatch);
+    else if (rows_per_half == 8) hipLaunchKernelGGL((sw_batch_kernel_pk16<8, false, false, true, true>), dim3(grid), dim3(64), 0, stream, dbatch);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 #elif PK16_PART == 1

@@ -183,7 +183,7 @@ class ManagerTable(C.Structure):
 ABI_SYMBOLS = [
     "mi355sw_create", "mi355sw_configure", "mi355sw_destroy", "mi355sw_last_error", "mi355sw_abi_version", "mi355sw_build_id",
     "mi355sw_get_capabilities", "mi355sw_get_score_parameters", "mi355sw_set_rows_per_lane",
-    "mi355sw_set_sequences", "mi355sw_unset_sequences", "mi355sw_align_partition", "mi355sw_align_partitions",
+    "mi355sw_set_sequences", "mi355sw_unset_sequences", "mi355sw_align_partition", "mi355sw_align_partitions", "mi355sw_set_goal_bounds",
     "mi355sw_process_block", "mi355sw_match_last_column", "mi355sw_progress",
     "mi355sw_processed_cells", "mi355sw_get_stats",
     "mi355sw_stream_begin", "mi355sw_seed_bound", "mi355sw_stream_feed_column", "mi355sw_stream_poll",
@@ -246,6 +246,7 @@ def load_library():
     lib.mi355sw_unset_sequences.argtypes = [H]
     lib.mi355sw_align_partition.argtypes = [H, C.POINTER(Partition), C.POINTER(ManagerTable), C.c_void_p]
     lib.mi355sw_align_partitions.argtypes = [H, C.c_int32, C.POINTER(Partition), C.POINTER(C.POINTER(ManagerTable)), C.POINTER(C.c_void_p)]
+    lib.mi355sw_set_goal_bounds.argtypes = [H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.mi355sw_process_block.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.POINTER(Score)]
     lib.mi355sw_match_last_column.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MatchResult)]
@@ -497,6 +498,16 @@ class MI355Aligner:
         if getattr(manager, "_callback_error", None):
             raise manager._callback_error
         del keep
+
+    def setGoalBounds(self, column_bounds, row_bounds=None):
+        """mi355sw_set_goal_bounds: goal pruning for the NEXT alignPartition (one bound) / alignPartitions (one per partition),
+        consumed by that call.  column_bounds[k] = goal - P - GAP_OPEN with P an upper bound of the forward values the last
+        column is matched against; row_bounds[k] the same for the border behind the last row; -INF / None: that term is off."""
+        cols = [int(b) for b in column_bounds]
+        rows = [-INF] * len(cols) if row_bounds is None else [-INF if b is None else int(b) for b in row_bounds]
+        assert len(rows) == len(cols)
+        n = len(cols)
+        self._check(self._lib.mi355sw_set_goal_bounds(self._h, n, (C.c_int32 * n)(*cols), (C.c_int32 * n)(*rows)), "setGoalBounds")
 
     batch_rows_per_lane_choices = (4, 8, 16)      # mi355sw_config.batch_rows_per_lane
 

@@ -43,6 +43,11 @@ class InitialCellsReader:
     def clone(self, offset):            # :65-71
         return InitialCellsReader(self.gap_open, self.gap_ext, self.start_offset + offset)
 
+    def peak_h(self):
+        """upper bound of the H of every cell of the border (goal pruning, AlignerManager.goalBounds): zeroes, or gap
+        penalties counted from a cell that holds 0"""
+        return 0
+
     def read(self, buf, length):
         if buf is None:                 # skip `length` cells (SpecialRowsPartition::continueFromLastRow reads into NULL)
             self.position += length
@@ -125,6 +130,11 @@ class ReversedCellsReader:
 
     def getOffset(self):
         return self.position
+
+    def peak_h(self):
+        """upper bound of the H of the cells still to be handed out, None when the border behind knows none"""
+        peak = getattr(self.reader, "peak_h", None)
+        return peak() if peak is not None else None
 
     def read(self, buf, length):
         length = min(length, self.position)
@@ -431,6 +441,7 @@ class AlignerManager:
         self.next_crosspoint = None          # (i, j, score, type)
         self.active = False
         self.last_column_pos = self.last_row_pos = 0
+        self.goal_bounds = None              # goalBounds() of the prepared sweep (stage2.prepare_next_crosspoint(prune_goal=True))
 
     # -- configuration (:191-316) ------------------------------------------------------------------------------
     def setSequences(self, seq0, seq1, i0, j0, i1, j1):
@@ -500,6 +511,33 @@ class AlignerManager:
         adj = self.prepareAlign(partition, start_type)
         if adj is not None:
             self.aligner.alignPartition(adj, self)
+
+    def goalBounds(self):
+        """(column bound, row bound) of the sweep as it stands prepared -- goal set, border readers seeked -- for the
+        aligner's setGoalBounds; None when the sweep must compute every cell.
+
+        The goal is met on the last column where reverse H + forward H == goal or reverse F + forward F + GAP_OPEN == goal
+        (matchLastColumn), the forward cells being the ones the last-column reader still has to hand out.  With P >= every
+        forward H of those (forward F <= H), a cell that meets the goal holds a reverse value >= goal - P - GAP_OPEN: the
+        column bound.  The same against the border behind the last-row reader, when this sweep is matched there too, is the
+        row bound (-INF: nobody reads the last row for the goal).  No bounds for a goal that may lie INSIDE the partition
+        (AT_ANYWHERE: the last piece of a local alignment), without a goal, or with a border whose peak is not known."""
+        if self.goal_score <= -INF or self.goal_location not in (AT_SEQUENCE_2, AT_SEQUENCE_1_OR_2):
+            return None
+        if self.last_column_reader is None or self.best_list is not None:
+            return None
+        peak = getattr(self.last_column_reader, "peak_h", None)
+        p_col = peak() if peak is not None else None
+        if p_col is None:
+            return None
+        row = -INF
+        if self.goal_location == AT_SEQUENCE_1_OR_2 and self.last_row_reader is not None:
+            peak = getattr(self.last_row_reader, "peak_h", None)
+            p_row = peak() if peak is not None else None
+            if p_row is None:
+                return None
+            row = self.goal_score - int(p_row) - GAP_OPEN
+        return self.goal_score - int(p_col) - GAP_OPEN, row
 
     def clone(self):
         """another manager on the same aligner and sequences, with state of its own: one per walk that runs side by side"""

@@ -53,11 +53,14 @@ def check_work_directory(work, seq0, seq1):
 
 @sra_mod.with_async_files
 def align(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end=AT_ANYWHERE, sra_limit=0,
-          block_pruning=True, max_partition_size=16, progress=None, max_alignments=1, ram_limit=0, prune_global=False):
+          block_pruning=True, max_partition_size=16, progress=None, max_alignments=1, ram_limit=0, prune_global=False,
+          prune_traceback=False):
     """seq0, seq1: fasta.Sequence.  Returns {"best", "alignment": stage56.Alignment or None, "text": bytes of
     alignment.00.txt or None when nothing scored above the floor, "crosspoints": {2: n, 3: n, 4: n},
     "seconds": {stage: s}}; with max_alignments > 1 also "alignments": one such record per end point stage 1 kept
-    (alignment.NN.txt, crosspoint_0S.NN, special_rows/stage.0S.NN: executeTraceback, libmasa.cpp:643-657)"""
+    (alignment.NN.txt, crosspoint_0S.NN, special_rows/stage.0S.NN: executeTraceback, libmasa.cpp:643-657).
+    prune_traceback: stage 2's sweeps skip what cannot meet their goal (stage2(prune_goal=True)); the same files but
+    special_rows/stage.02.NN, whose cells off every goal path may be lower bounds"""
     check_work_directory(work, seq0, seq1)
     # the data the aligner compares: forward or reversed, complemented, N-cleared (fasta.py); --trim only selects the
     # part of the matrix stage 1 sweeps, every coordinate of every stage stays absolute (Sequence.cpp:117-159)
@@ -76,20 +79,20 @@ def align(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end=
         return out                                        # an empty best-score list: MASA-Core runs no traceback either
     for ident in range(max(len(r1.get("bests", [])), 1)):
         rec = _traceback(aligner, seq0, seq1, d0, d1, work, ident, alignment_start, sra_limit, max_partition_size, bounds, secs,
-                         ram_limit, areas)
+                         ram_limit, areas, prune_traceback)
         out["alignments"].append(rec)
     out.update(out["alignments"][0])
     return out
 
 
 def _traceback(aligner, seq0, seq1, d0, d1, work, ident, alignment_start, sra_limit, max_partition_size, bounds, secs,
-               ram_limit=0, areas=None):
+               ram_limit=0, areas=None, prune_traceback=False):
     """stages 2-6 for the alignment that ends in crosspoint_01.<ident>"""
     def clock(stage, t0):
         secs[stage] = secs.get(stage, 0.0) + time.time() - t0
     t = time.time()
     r2 = stage2(aligner, d0, d1, work, alignment_start=alignment_start, sra_limit=sra_limit, ident=ident, bounds=bounds,
-                ram_limit=ram_limit, areas=areas)
+                ram_limit=ram_limit, areas=areas, prune_goal=prune_traceback)
     clock(2, t)
     t = time.time()
     r3 = stage3(aligner, d0, d1, work, sra_limit=sra_limit, ident=ident, ram_limit=ram_limit, areas=areas)

@@ -298,6 +298,22 @@ class SpecialRowReader:
             raise RuntimeError("end of special row %s: %d cells at %d, file ends after %d" % (fn, length, offset, a.shape[0]))
         return a
 
+    def peak_h(self):
+        """upper bound of the H of the cells this reader can still hand out -- cells [0, offset), the border cell included
+        (SpecialRowsPartition.row_peak leaves that one out): the row's recorded peak where it lies among them (it is the
+        peak of the whole row), the cells themselves otherwise.  None for an empty range."""
+        if self.offset <= 0:
+            return None
+        if self.id == 0:
+            peak = getattr(self.partition.first_row_reader, "peak_h", None)
+            if peak is not None:
+                return peak()
+        else:
+            p = self.partition.peaks.get(self.id)
+            if p is not None and 0 <= p[1] < self.offset:
+                return p[0]
+        return int(np.max(self._cells(0, self.offset)[:, 0]))
+
     def read(self, buf, length):
         if self.offset == 0:
             raise RuntimeError("special row overflow: %d cells asked from row %08X at its start" % (length, self.id))

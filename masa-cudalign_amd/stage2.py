@@ -18,7 +18,7 @@ import time
 
 import numpy as np
 
-from .engine import NEEDLEMAN_WUNSCH, Partition
+from .engine import NEEDLEMAN_WUNSCH, Partition, INF
 from .manager import (AlignerManager, InitialCellsReader, ReversedCellsReader, BacktraceLost, AT_ANYWHERE,
                       AT_SEQUENCE_1_OR_2, GAP_OPEN, GAP_EXT, INIT_WITH_GAPS, INIT_WITH_GAPS_OPENED)
 from .crosspoints import Crosspoint, CrosspointsFile, crosspoint_file, TYPE_MATCH, TYPE_GAP_1, TYPE_GAP_2
@@ -41,11 +41,38 @@ def _as_u8(seq):
     return np.frombuffer(bytes(seq), dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else np.asarray(seq, dtype=np.uint8)
 
 
-def prepare_next_crosspoint(mgr, area, c0, c1, alignment_start, must_find=True, goal_location=None, scratch=False):
+class _SweepCells:
+    """what the sweeps of one stage cost, from the aligner's statistics: one record per aligner call"""
+
+    def __init__(self):
+        self.calls = []
+
+    def add(self, aligner, widths, bounded):
+        st = aligner.getStatistics() if hasattr(aligner, "getStatistics") else {}
+        self.calls.append({"widths": [int(w) for w in widths], "bounded": [bool(b) for b in bounded],
+                           "processed_cells": int(st.get("processed_cells", 0)), "pruned_cells": int(st.get("pruned_cells", 0)),
+                           "kernel": st.get("kernel", "")})
+
+    def total(self, key):
+        return sum(c[key] for c in self.calls)
+
+
+def _hand_goal_bounds(aligner, managers):
+    """goal pruning: the bounds of the prepared sweeps (AlignerManager.goal_bounds) for the aligner's next call"""
+    bounds = [m.goal_bounds for m in managers]
+    if any(b is not None for b in bounds):
+        if not hasattr(aligner, "setGoalBounds"):
+            raise RuntimeError("prune_goal needs an aligner with setGoalBounds")
+        aligner.setGoalBounds([b[0] if b is not None else -INF for b in bounds], [b[1] if b is not None else -INF for b in bounds])
+    return [b is not None for b in bounds]
+
+
+def prepare_next_crosspoint(mgr, area, c0, c1, alignment_start, must_find=True, goal_location=None, scratch=False, prune_goal=False):
     """the set-up of find_next_crosspoint: goal, borders and special-rows partition of the sweep c0 -> c1.  Returns
     (special-rows partition, partition for the aligner or None if the manager met the goal without it).
     scratch: the special-rows partition is made under a name no reader looks for (a sweep from a guessed crosspoint: it
-    moves into place when the walk accepts it, SpecialRowsArea.truncate_partition)."""
+    moves into place when the walk accepts it, SpecialRowsArea.truncate_partition).
+    prune_goal: the sweep's goal bounds (AlignerManager.goalBounds) are left in mgr.goal_bounds for whoever calls the aligner."""
     first_row = InitialCellsReader(0 if c0.type == TYPE_GAP_1 else GAP_OPEN, GAP_EXT)
     first_col = InitialCellsReader(0 if c0.type == TYPE_GAP_2 else GAP_OPEN, GAP_EXT)
     if not must_find:
@@ -65,6 +92,7 @@ def prepare_next_crosspoint(mgr, area, c0, c1, alignment_start, must_find=True, 
     except BaseException:
         part.close()
         raise
+    mgr.goal_bounds = mgr.goalBounds() if (prune_goal and must_find and adj is not None) else None
     return part, adj
 
 
@@ -82,13 +110,17 @@ def conclude_next_crosspoint(mgr, area, part, c0, c1, must_find=True):
     return Crosspoint(i, j, score, typ)
 
 
-def find_next_crosspoint(mgr, area, c0, c1, alignment_start, must_find=True, goal_location=None):
+def find_next_crosspoint(mgr, area, c0, c1, alignment_start, must_find=True, goal_location=None, prune_goal=False, cells=None):
     """sw_stage2.cpp:49-129 / sw_stage3.cpp:49-122: aligns partition c0 -> c1 (both in the coordinates of the running
-    orientation), returns the crosspoint where the goal c0.score is met on the last column / last row / inside"""
-    part, adj = prepare_next_crosspoint(mgr, area, c0, c1, alignment_start, must_find, goal_location)
+    orientation), returns the crosspoint where the goal c0.score is met on the last column / last row / inside.
+    prune_goal: the sweep skips what cannot meet its goal (goal pruning); cells: a _SweepCells that counts it"""
+    part, adj = prepare_next_crosspoint(mgr, area, c0, c1, alignment_start, must_find, goal_location, prune_goal=prune_goal)
     if adj is not None:
         try:
+            bounded = _hand_goal_bounds(mgr.aligner, [mgr]) if prune_goal else [False]
             mgr.aligner.alignPartition(adj, mgr)
+            if cells is not None:
+                cells.add(mgr.aligner, [adj.j1 - adj.j0], bounded)
         except BaseException:
             part.close()
             raise
@@ -143,7 +175,7 @@ class _Speculation:
     stage2(speculate=False) or MI355SW_STAGE2_SPECULATE=0 walks the plain chain.  The row maxima are recorded by stage 1 while
     it writes the rows (SpecialRowsPartition.peaks), read back from the rows where they were not."""
 
-    def __init__(self, mgr, area, part1, cp, col_reader, len_v, len_h, alignment_start):
+    def __init__(self, mgr, area, part1, cp, col_reader, len_v, len_h, alignment_start, prune_goal=False, cells=None):
         self.area = area
         self.sweeps = {}
         self.made = self.accepted = self.discarded = 0
@@ -195,7 +227,7 @@ class _Speculation:
                     col = ReversedCellsReader(col_reader)
                     col.seek(c0_r.i - part1.i0 + 1)
                     m.setLastRowReader(col)
-                part, adj = prepare_next_crosspoint(m, area, c0, c1p, alignment_start, scratch=guess)
+                part, adj = prepare_next_crosspoint(m, area, c0, c1p, alignment_start, scratch=guess, prune_goal=prune_goal)
                 sw = dict(mgr=m, part=part, c0=c0, c1=c1, guess=guess)
                 self.sweeps[(c0.astuple(), c1.astuple())] = sw
                 if adj is not None:
@@ -206,10 +238,16 @@ class _Speculation:
                 # (1024-row strips: 4.6 TCUPS against the 2.7 of the 256-row strips stage 3's small partitions get); on an
                 # aligner at engine-picked heights the batch saves its rows on the chain's 2048-row grid whatever its height
                 kw = {"rows_per_lane": 16} if 16 in getattr(mgr.aligner, "batch_rows_per_lane_choices", ()) else {}
+                bounded = _hand_goal_bounds(mgr.aligner, [m for m, _ in jobs]) if prune_goal else [False] * len(jobs)   # one bound per guessed sweep
                 mgr.aligner.alignPartitions([a for _, a in jobs], [m for m, _ in jobs], **kw)
+                if cells is not None:
+                    cells.add(mgr.aligner, [a.j1 - a.j0 for _, a in jobs], bounded)
             else:
                 for m, a in jobs:
+                    bounded = _hand_goal_bounds(mgr.aligner, [m]) if prune_goal else [False]
                     mgr.aligner.alignPartition(a, m)
+                    if cells is not None:
+                        cells.add(mgr.aligner, [a.j1 - a.j0], bounded)
         except BaseException:
             self.discard_rest()
             raise
@@ -240,16 +278,22 @@ class _Speculation:
 
 @sra_mod.with_async_files
 def stage2(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, sra_limit=0, ident=0, bounds=None, ram_limit=0,
-           areas=None, speculate=None):
+           areas=None, speculate=None, prune_goal=False):
     """Runs stage 2 for alignment `ident` of work directory `work` (stage 1 must have left crosspoint_01.NN and,
     with sra_limit > 0, its special rows there).  seq0 / seq1: the whole sequences; `bounds` = (i0, j0, i1, j1) the
     part --trim selected for stage 1 (only its origin matters here: where a global alignment must begin).  Returns {"crosspoints": [(type, i, j, score), ...] as written to
     crosspoint_02.NN, "end": the last crosspoint in ORIGINAL coordinates, "partitions", "seconds"}.
-    speculate: sweeps from guessed crosspoints side by side (_Speculation); None = on unless MI355SW_STAGE2_SPECULATE=0."""
+    speculate: sweeps from guessed crosspoints side by side (_Speculation); None = on unless MI355SW_STAGE2_SPECULATE=0.
+    prune_goal: goal pruning -- every sweep whose goal lies on its last column hands the aligner the bounds of what can
+    still meet it (AlignerManager.goalBounds, MI355Aligner.setGoalBounds) and skips the rest; the crosspoints are the same,
+    the special rows saved for stage 3 are exact wherever a path to a goal runs.  Off: every launch as before.
+    The result also carries "processed_cells" / "pruned_cells" summed over the stage's sweeps and "sweeps", one record per
+    aligner call."""
     t_start = time.time()
     if speculate is None:
         speculate = speculation_default()
     guessed = {"sweeps": 0, "accepted": 0, "discarded": 0}
+    cells = _SweepCells()
     s0, s1 = _as_u8(seq0), _as_u8(seq1)
     m, n = len(s0), len(s1)
     seq_v = np.ascontiguousarray(s1[::-1])               # sw_stage2.cpp:258-276: reverse = 1
@@ -304,7 +348,7 @@ def stage2(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, sra_limit=0, 
             spec = None
             try:
                 if speculate:
-                    spec = _Speculation(mgr, area2, part1, cp, col_reader, len_v, len_h, alignment_start)
+                    spec = _Speculation(mgr, area2, part1, cp, col_reader, len_v, len_h, alignment_start, prune_goal=prune_goal, cells=cells)
                 while True:
                     cp_r = cp.reverse(len_v, len_h)
                     if alignment_start == AT_ANYWHERE and cp.score <= 0:
@@ -325,7 +369,7 @@ def stage2(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, sra_limit=0, 
                     if done is not None:
                         cp = conclude_next_crosspoint(done["mgr"], area2, done["part"], cp, c1)
                     else:
-                        cp = find_next_crosspoint(mgr, area2, cp, c1, alignment_start)
+                        cp = find_next_crosspoint(mgr, area2, cp, c1, alignment_start, prune_goal=prune_goal, cells=cells)
                     partitions += 1
                     out.write(cp)
                     if cp.type != TYPE_MATCH:
@@ -351,4 +395,5 @@ def stage2(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, sra_limit=0, 
     finally:
         out.close()
     return {"crosspoints": out.tuples(), "end": cp_r.astuple(), "partitions": partitions, "seconds": time.time() - t_start,
-            "speculation": guessed if speculate else None}
+            "speculation": guessed if speculate else None, "processed_cells": cells.total("processed_cells"),
+            "pruned_cells": cells.total("pruned_cells"), "sweeps": cells.calls}

@@ -6,7 +6,8 @@ MASA-Core's own stages on top of the engine.
 
 Related pair from seqgen (cfg as in BASELINE.md section 2), local alignment, block pruning on.  Checks: the text
 re-scores itself to the best score (stage 5 refuses anything else), and -- for sizes the oracle finishes in seconds --
-the best score equals the oracle's.  `MI355SW_WORK` overrides the work directory (default: a temporary one, removed)."""
+the best score equals the oracle's.  `MI355SW_WORK` overrides the work directory (default: a temporary one, removed);
+`MI355SW_PRUNE_TRACEBACK=1` runs stage 2 with goal pruning (pipeline.align(prune_traceback=True))."""
 import json
 import os
 import shutil
@@ -48,7 +49,8 @@ def main():
         pipeline.stage2 = profiled_stage2
     t0 = time.time()
     try:
-        out = pipeline.align(al, q0, q1, work, sra_limit=limit)
+        prune_tb = os.environ.get("MI355SW_PRUNE_TRACEBACK", "") not in ("", "0")
+        out = pipeline.align(al, q0, q1, work, sra_limit=limit, prune_traceback=prune_tb)
     finally:
         al.close()
     total = time.time() - t0
@@ -58,6 +60,8 @@ def main():
            "stage1_gcups": out["stage1"]["gcups"], "stage1_kernel_ms": out["stage1"].get("kernel_ms"),
            "stage1_strip_rows": out["stage1"].get("strip_rows"), "stage1_pruned_fraction": out["stage1"].get("pruned_cells", 0) / float(m) / n,
            "stage3_rounds": out.get("stage3", {}).get("rounds"), "stage2_speculation": out.get("stage2", {}).get("speculation"),
+           "prune_traceback": prune_tb, "stage2_processed_cells": out.get("stage2", {}).get("processed_cells"),
+           "stage2_pruned_cells": out.get("stage2", {}).get("pruned_cells"), "build_id": pkg.engine.library_build_id(),
            "stage4": out.get("stage4"), "alignment_score": out["alignment"].raw_score if out["alignment"] else None,
            "text_bytes": len(out["text"]) if out["text"] else 0}
     # the same digests tools/dropin_scale.py records for MASA-Core's own stages on the engine: equal = the same files
