@@ -121,8 +121,11 @@ typedef struct {
 #define MI355SW_F_DETERMINISTIC_PRUNE 16384 /* reproducible special rows under block pruning: a strip tests against the bound as it stood a fixed number
                                                of strips above it (plus its own finds) instead of against the newest value any wavefront has
                                                published -- WHICH slabs go is then a function of the input, as in the reference, whose pruning
-                                               window is set on the host between two diagonals (BlockPruningDiagonal.cpp:109-152).  Two runs, or an
-                                               interrupted and resumed run and an uninterrupted one, leave the same special rows.  Costs nothing
+                                               window is set on the host between two diagonals (BlockPruningDiagonal.cpp:109-152).  Two runs of one
+                                               input leave the same special rows; so do an interrupted and resumed run and an uninterrupted one
+                                               when the resumed run is started from the state saved with the row it continues from
+                                               (mi355sw_get_prune_state / mi355sw_set_prune_state) -- without it the resumed run's bound starts
+                                               afresh and its rows are other, equally valid lower bounds.  Costs nothing
                                                where the bound starts from the seed; a bound that grows with the sweep arrives one round of
                                                wavefronts later.  A stream on its own only (the bands of a chain share their finds as they arrive) */
 #define MI355SW_F_NO_GOAL_SWEEP_HEIGHTS 32768 /* mi355sw_align_partition leaves the strip height of a sweep that looks goal-stopped (MASA-Core's stages 2 and 3,
@@ -277,6 +280,35 @@ int mi355sw_align_partitions(mi355sw_handle* h, int32_t count, const mi355sw_par
  * MI355SW_F_FORCE_INT32, an overflow rerun -- computes every cell.  No probe or seed runs and MI355SW_EBOUND does not apply
  * (the bound is not the score of a last cell).  mi355sw_stats.pruned_cells / processed_cells / kernel report it. */
 int mi355sw_set_goal_bounds(mi355sw_handle* h, int32_t count, const int32_t* column_bounds, const int32_t* row_bounds);
+
+/* Pruning state of a reproducibly pruned run (MI355SW_F_DETERMINISTIC_PRUNE; additive in ABI 8): what a run that continues
+ * from a special row needs to skip exactly the slabs the uninterrupted run skips below that row.
+ * In that mode strip s tests against prefix[max(0, s - lag)], the bound as it stood `lag` strips above it.  The state of a
+ * special row at DP row r = s0 * strip_rows is the lag + 1 words
+ *   words[k] = prefix[max(0, s0 - lag + k)],  k = 0 .. lag
+ * (the engine's own score domain: opaque to the caller), with strip_rows and lag.  words[lag] is everything known above the
+ * row, what the first run's probe, seed or warm-up pass found included.
+ *
+ * mi355sw_get_prune_state: the state of the special row `row` (the coordinate dispatch_row is given), from inside
+ * dispatch_row for that row and afterwards until the next special row is handed over.  *count = 0: no state -- the flag is
+ * off, the int32 family runs (forced, or after an overflow rerun), the stream shares its best (share_best), or the row is
+ * not a strip boundary (768- and 1536-row strips on the 2048-row grid).  MI355SW_EINVAL with *count set when `capacity`
+ * words are too few.  mi355sw_align_partition fetches the words before it hands the row over (device-to-host, on the copy
+ * stream that carries the row; the kernel's stream is never waited for); mi355sw_stream_* callers get no state.
+ *
+ * mi355sw_set_prune_state: the NEXT mi355sw_stream_begin / mi355sw_align_partition starts from this state and consumes it:
+ * the packed pruning kernels at strip_rows, at most `lag` wavefronts in flight, no probe, no seed, no warm-up pass, and neither
+ * initial_bound nor anything else folded into the words (the uninterrupted run's strip s0 had not seen the finds of strips
+ * s0 - lag .. s0 - 1 either).  Its partition's first row is the special row the state was saved with.  MI355SW_EINVAL, with
+ * the reason in mi355sw_last_error, when the state cannot be honoured: count != lag + 1, a strip height that is not built,
+ * rows_per_lane fixed to another height, MI355SW_F_FORCE_INT32, MI355SW_F_DETERMINISTIC_PRUNE off -- here, or in the call
+ * that would consume it (a partition that does not prune, share_best, a column port).  The state of a resumed run can be
+ * taken and handed on in turn.  MI355SW_EBOUND applies against words[lag] where that is a bound of the cell the resumed
+ * partition ends in (global alignments); the best score of a LOCAL alignment may lie above the first row of a resumed
+ * partition, which then rightly ends below it. */
+int mi355sw_get_prune_state(mi355sw_handle* h, int32_t row, int32_t* out_words, int32_t capacity, int32_t* count,
+                            int32_t* strip_rows, int32_t* lag);
+int mi355sw_set_prune_state(mi355sw_handle* h, const int32_t* words, int32_t count, int32_t strip_rows, int32_t lag);
 
 /* AbstractBlockProcessor::processBlock (M/libmasa/processors/AbstractBlockProcessor.hpp:27-37,
  * semantics CPUBlockProcessor.cpp:95-112): row[k] = (H,F) of (i0-1,j0+k) in/out, col[0] = diagonal

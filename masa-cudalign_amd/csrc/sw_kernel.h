@@ -92,11 +92,11 @@ struct KernelArgs {
     // timing: two runs of one input leave different lower bounds off the optimal paths in their special rows.  The reference
     // decides its pruning window on the host between two external diagonals (BlockPruningDiagonal::updatePruningWindow,
     // BlockPruningDiagonal.cpp:109-152): a function of the input.  In this mode strip s tests against
-    //   det_prefix[max(0, s - det_lag)] = max(what the run started from, what strips 0 .. s - det_lag - 1 found)
+    //   det_prefix[max(det_floor, s - det_lag)] = max(what the run started from, what strips 0 .. s - det_lag - 1 found)
     // -- final when strip s starts (completion is ordered, at most det_lag strips are ever in flight) -- and against what IT
     // has found so far, left to right.  det_news[s]: what strip s found (T domain), folded into the prefix by
     // complete_strip_common.  Entries not yet written hold DET_UNSET; a reader waits for them (it never has to, see above).
-    int* det_prefix;             // [strips + 1]
+    int* det_prefix;             // [strips + 1], behind -det_floor words of saved history (see det_floor)
     int* det_news;               // [strips]
     int det_lag;
     const int* gbest_in;         // where the strips READ the running best from: gbest itself, or a word that stays at -INF
@@ -109,6 +109,13 @@ struct KernelArgs {
     // T domain like gbest; constants of the sweep, so which slabs go is a function of the input.  -INF: that term is off
     // (nobody reads that border for the goal).
     int goal_bound_col = -999999999, goal_bound_row = -999999999;   // (the only members with an initialiser: KernelArgs{} is "no goal")
+    // ---- reproducible pruning of a stream that CONTINUES another one (mi355sw_set_prune_state) ----
+    // Strip s reads det_prefix[max(det_floor, s - det_lag)].  0: the stream starts the sweep, prefix[0] is what it began with.
+    // -det_lag: the det_lag + 1 words in front of and at det_prefix[0] are the history the first run saved with the row this
+    // stream starts from -- det_prefix[k - det_lag] = what strip k of this stream would have read had the sweep never stopped --
+    // so every strip reads its own word and the clamp never acts.  The hand-over (complete_strip_common) is the same for both.
+    // (last member: the layout the kernels without pruning read stays as it was)
+    int det_floor;
 };
 
 // The argument block lives in device memory and is read through the constant address space with a

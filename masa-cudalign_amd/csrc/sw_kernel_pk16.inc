@@ -710,7 +710,8 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
     // reproducible pruning (KernelArgs::det_prefix): the bound this strip tests against is a word that is final before the strip
     // starts -- what the run began with and what the strips det_lag and more above found -- plus what the strip itself finds
     const bool det = prune_on && !GOAL && a->det_prefix != nullptr;
-    const int* const gbest_inp = pin_ptr16(det ? (const int*) &a->det_prefix[max(0, s - a->det_lag)] : a->gbest_in);
+    // (det_floor: 0, or -det_lag in a stream that continues from a saved state, whose history lies in front of det_prefix[0])
+    const int* const gbest_inp = pin_ptr16(det ? (const int*) &a->det_prefix[max(a->det_floor, s - a->det_lag)] : a->gbest_in);
     if (det) {
         int spins = 0;
         while (poll_agent16(gbest_inp) == DET_UNSET && spins < spin_limit) { __builtin_amdgcn_s_sleep(8); spins++; }

@@ -184,6 +184,7 @@ ABI_SYMBOLS = [
     "mi355sw_create", "mi355sw_configure", "mi355sw_destroy", "mi355sw_last_error", "mi355sw_abi_version", "mi355sw_build_id",
     "mi355sw_get_capabilities", "mi355sw_get_score_parameters", "mi355sw_set_rows_per_lane",
     "mi355sw_set_sequences", "mi355sw_unset_sequences", "mi355sw_align_partition", "mi355sw_align_partitions", "mi355sw_set_goal_bounds",
+    "mi355sw_get_prune_state", "mi355sw_set_prune_state",
     "mi355sw_process_block", "mi355sw_match_last_column", "mi355sw_progress",
     "mi355sw_processed_cells", "mi355sw_get_stats",
     "mi355sw_stream_begin", "mi355sw_seed_bound", "mi355sw_stream_feed_column", "mi355sw_stream_poll",
@@ -247,6 +248,8 @@ def load_library():
     lib.mi355sw_align_partition.argtypes = [H, C.POINTER(Partition), C.POINTER(ManagerTable), C.c_void_p]
     lib.mi355sw_align_partitions.argtypes = [H, C.c_int32, C.POINTER(Partition), C.POINTER(C.POINTER(ManagerTable)), C.POINTER(C.c_void_p)]
     lib.mi355sw_set_goal_bounds.argtypes = [H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mi355sw_get_prune_state.argtypes = [H, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mi355sw_set_prune_state.argtypes = [H, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32]
     lib.mi355sw_process_block.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.POINTER(Score)]
     lib.mi355sw_match_last_column.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MatchResult)]
@@ -508,6 +511,31 @@ class MI355Aligner:
         assert len(rows) == len(cols)
         n = len(cols)
         self._check(self._lib.mi355sw_set_goal_bounds(self._h, n, (C.c_int32 * n)(*cols), (C.c_int32 * n)(*rows)), "setGoalBounds")
+
+    def pruneState(self, row):
+        """mi355sw_get_prune_state: the pruning state of the special row `row` (the coordinate dispatchRow is given) of a
+        reproducibly pruned run (F_DETERMINISTIC_PRUNE) -- {"row", "words", "strip_rows", "lag"} -- from inside dispatchRow for
+        that row until the next special row; None when there is none (flag off, int32 family, a row off the strip grid)."""
+        cap = 4096
+        while True:
+            words = (C.c_int32 * cap)()
+            count, rows, lag = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+            rc = self._lib.mi355sw_get_prune_state(self._h, int(row), words, cap, C.byref(count), C.byref(rows), C.byref(lag))
+            if rc != 0 and count.value > cap:
+                cap = count.value
+                continue
+            self._check(rc, "pruneState")
+            if count.value == 0:
+                return None
+            return {"row": int(row), "words": [int(w) for w in words[:count.value]], "strip_rows": rows.value, "lag": lag.value}
+
+    def setPruneState(self, words, strip_rows, lag):
+        """mi355sw_set_prune_state: the NEXT alignPartition continues a reproducibly pruned run from the special row these
+        words were saved with (pruneState) and skips what the uninterrupted run skips; consumed by that call.  AlignerError
+        (EINVAL) when the engine as configured cannot honour the state -- the caller then resumes without it."""
+        self._sync_config()
+        w = [int(x) for x in words]
+        self._check(self._lib.mi355sw_set_prune_state(self._h, (C.c_int32 * len(w))(*w), len(w), int(strip_rows), int(lag)), "setPruneState")
 
     batch_rows_per_lane_choices = (4, 8, 16)      # mi355sw_config.batch_rows_per_lane
 

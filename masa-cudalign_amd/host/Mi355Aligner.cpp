@@ -220,6 +220,16 @@ int32_t Mi355Aligner::cbPrune(void* u) {
 }
 #undef SELF
 
+int Mi355Aligner::getPruneState(int row, int* words, int capacity, int* count, int* stripRows, int* lag) {
+    initialize();
+    return mi355sw_get_prune_state(handle, row, words, capacity, count, stripRows, lag);
+}
+
+int Mi355Aligner::setPruneState(const int* words, int count, int stripRows, int lag) {
+    initialize();
+    return mi355sw_set_prune_state(handle, words, count, stripRows, lag);
+}
+
 void Mi355Aligner::clearStatistics() { statCells = 0; statKernelMs = 0; statPartitions = 0; statPruned = 0; }
 void Mi355Aligner::printInitialStatistics(FILE* file) {
     char name[128]; int cus = 0, mhz = 0; long long bytes = 0;

@@ -43,6 +43,13 @@ public:
     int refineCrosspoints(const char* seq0, const char* seq1, int seq0_len, int seq1_len, const int* in_tijs, int count,
                           int max_partition_size, int** out_tijs, int* out_count, double* kernel_ms);
 
+    /* Reproducible pruning across a resume (mi355sw_get_prune_state / mi355sw_set_prune_state, include/mi355sw.h), passed
+     * through for a stage driver that keeps the state next to its status file, as the native stage1.py does.  MASA-Core's
+     * IManager cannot carry it: under the core's own resume (SpecialRowsPartition::continueFromLastRow) nobody calls these,
+     * and the run continues as it always did.  Both return the C ABI's code (MI355SW_OK, MI355SW_EINVAL: see the header). */
+    int getPruneState(int row, int* words, int capacity, int* count, int* stripRows, int* lag);
+    int setPruneState(const int* words, int count, int stripRows, int lag);
+
 private:
     void check(int rc, const char* what);
     /* IManager trampolines (M/libmasa/IManager.hpp:98-313) */

@@ -283,6 +283,7 @@ class Stage1Manager:
         # SpecialRowsPartition::write, AlignerManager.cpp:334-356); the status file follows every completed row
         self.sra, self.status = sra_partition, status
         self.value_best = None      # (score, row_lo, row_hi): best strip VALUE of a two-phase run (dispatchStripValue)
+        self.aligner = None         # set by whoever runs the partition (stage1.py): asked for the pruning state of every row saved
         self.active = True
         self.special_rows = {}      # dp row -> list of chunks
         self.last_row_chunks, self.last_column_chunks = [], []
@@ -329,6 +330,15 @@ class Stage1Manager:
         if self.sra is not None:
             if self.sra.write(i, buf[:length]) and self.status is not None:
                 self.status.last_special_row = i
+                # reproducible pruning: what a run that continues from this row must start from, saved in the same write
+                # (an aligner without the method -- the CPU block aligner -- or without a state: a resume as before)
+                state = None
+                aligner = getattr(self, "aligner", None)
+                if hasattr(aligner, "pruneState"):
+                    state = aligner.pruneState(i - self.seq0_offset)
+                    if state is not None:
+                        state = dict(state, row=i)
+                self.status.set_prune_state(state)
                 self.status.merge_value_best(self.value_best)
                 self.status.save(self.best_list.best)
         elif self.mustDispatchSpecialRows():

@@ -731,7 +731,11 @@ def get_area(areas, work, stage, ident=0, deep=-1, ram_limit=0, disk_limit=1):
 class Status:
     """M/common/Status.cpp:40-89: stage, last special row, best score; saved through a temporary file + rename.
     Next to it (own file `status.mi355`, MASA-Core never looks at it): the best strip VALUE of a two-phase run whose
-    cell has not been located yet -- "score row_lo row_hi" -- see stage1.py."""
+    cell has not been located yet -- "score row_lo row_hi [key]" -- and, on a line of its own, the pruning state of
+    `last_special_row` in a reproducibly pruned run -- "prune_state row strip_rows lag [key] count words..." (the engine's
+    pruneState / setPruneState) -- see stage1.py.  Both belong to the partition `value_key` names.  The side file is replaced
+    BEFORE the status file, so it also keeps the line of the row saved before: whichever row the status file names after a
+    kill between the two renames, its state is there."""
 
     def __init__(self, work):
         self.file = os.path.join(work, "status")
@@ -740,14 +744,20 @@ class Status:
         self.stage, self.last_special_row, self.best = 1, 0, None
         self.value_best = None
         self.value_key = None          # what the value belongs to: (i0, j0, i1, j1, alignment start, alignment end)
+        self.prune_state = None        # {"row", "strip_rows", "lag", "words"} of last_special_row, or None
+        self._older_state = None       # ... and of the row saved before it (see above)
         self.loaded = False
         _files.drain()
         if os.path.exists(self.side):
-            tok = open(self.side).read().split()
-            if len(tok) >= 3:
-                self.value_best = (int(tok[0]), int(tok[1]), int(tok[2]))
-            if len(tok) >= 9:
-                self.value_key = tuple(int(x) for x in tok[3:9])
+            for line in open(self.side).read().splitlines():
+                tok = line.split()
+                if tok and tok[0] == "prune_state":
+                    self._load_prune_state(tok[1:])
+                    continue
+                if len(tok) >= 3:
+                    self.value_best = (int(tok[0]), int(tok[1]), int(tok[2]))
+                if len(tok) >= 9:
+                    self.value_key = tuple(int(x) for x in tok[3:9])
         # Status::load (Status.cpp:40-66) falls back to the temporary file when a kill fell between its write and the rename
         src = self.file if os.path.exists(self.file) else (self.tmp if os.path.exists(self.tmp) else None)
         if src is not None:
@@ -757,6 +767,44 @@ class Status:
                 if len(tok) >= 5:
                     self.best = (int(tok[2]), int(tok[3]), int(tok[4]))
                 self.loaded = True
+        if self.prune_state is not None and self.prune_state["row"] != self.last_special_row:
+            # killed between the two renames: the status file still names the row before
+            older = self._older_state
+            self.prune_state = older if older is not None and older["row"] == self.last_special_row else None
+        self._older_state = None
+
+    def _load_prune_state(self, tok):
+        """row strip_rows lag key(6) count words(count); a line cut short by a kill is no state"""
+        try:
+            v = [int(x) for x in tok]
+        except ValueError:
+            return
+        if len(v) < 10 or len(v) != 10 + v[9] or v[9] != v[2] + 1:
+            return
+        if self.value_key is not None and self.value_key != tuple(v[3:9]):
+            return
+        self.value_key = tuple(v[3:9])
+        self._older_state, self.prune_state = self.prune_state, {"row": v[0], "strip_rows": v[1], "lag": v[2], "words": v[10:]}
+
+    def claim(self, key, resumed):
+        """what the side file holds only counts for the run that continues THAT partition: dropped for another key, or a
+        run that starts afresh"""
+        if not resumed or self.value_key != key:
+            self.value_best = None
+            self.prune_state = self._older_state = None
+        self.value_key = key
+
+    def set_prune_state(self, state):
+        """the state of the row `last_special_row` is about to name (None: it has none); the one it replaces stays in the
+        side file for one more save"""
+        if self.prune_state is not None:
+            self._older_state = self.prune_state
+        self.prune_state = state
+
+    def prune_state_for(self, row):
+        """the saved state when it is the one of `row`, else None"""
+        st = self.prune_state
+        return st if st is not None and st["row"] == row else None
 
     def merge_value_best(self, cand):
         """keep the FIRST strip that reaches the largest value (canonical order: smallest i wins ties)"""
@@ -772,6 +820,12 @@ class Status:
             if self.value_key is not None:
                 side += " %d %d %d %d %d %d" % tuple(self.value_key)
             side += "\n"
+        ps = self.prune_state
+        if ps is not None and ps["row"] == self.last_special_row and self.value_key is not None:
+            for st in (self._older_state, ps):
+                if st is not None and (st is ps or st["row"] != ps["row"]):
+                    side = (side or "") + "prune_state %d %d %d " % (st["row"], st["strip_rows"], st["lag"]) + \
+                        "%d %d %d %d %d %d " % tuple(self.value_key) + "%d " % len(st["words"]) + " ".join("%d" % w for w in st["words"]) + "\n"
         if best is not None:
             self.best = tuple(int(x) for x in best)
         b = self.best if self.best is not None else (-1, -1, -INF)
@@ -788,7 +842,7 @@ class Status:
 
     def drop_value_best(self):
         """stage 1 is complete: the value-only record of a two-phase run has served its purpose"""
-        self.value_best = self.value_key = None
+        self.value_best = self.value_key = self.prune_state = self._older_state = None
         _files.drain()
         for fn in (self.side, self.side + ".tmp"):
             if os.path.exists(fn):

@@ -7,7 +7,7 @@ best score as an uninterrupted one."""
 import os
 import time
 
-from .engine import Partition, F_NO_DIAGONAL_SEED
+from .engine import Partition, F_NO_DIAGONAL_SEED, AlignerError
 from .manager import (Stage1Manager, ArrayCellsReader, InitialCellsReader, AT_ANYWHERE, AT_SEQUENCE_1, AT_SEQUENCE_2,
                       AT_SEQUENCE_1_OR_2, GAP_OPEN, GAP_EXT)
 from . import sra as sra_mod
@@ -88,7 +88,8 @@ def stage1(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end
     row on disk.
     `max_alignments` > 1 (--max-alignments): the best-score list keeps that many end points of different alignments
     (BestScoreList), one crosspoint_01.NN each; candidates are what the aligner dispatches (one best cell per strip).
-    Returns {"best": (i, j, score) in 1-based DP coordinates, "bests": the whole list, "resumed_from": row or None, "seconds", "gcups", ...}."""
+    Returns {"best": (i, j, score) in 1-based DP coordinates, "bests": the whole list, "resumed_from": row or None,
+    "reproducible_resume": the run continued from a saved pruning state, "seconds", "gcups", ...}."""
     m, n = len(seq0), len(seq1)
     bi0, bj0, bi1, bj1 = bounds if bounds is not None else (0, 0, m, n)
     if not (0 <= bi0 < bi1 <= m and 0 <= bj0 < bj1 <= n):
@@ -105,7 +106,7 @@ def stage1(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end
         last = part_sra.last_disk_row_id()
         if last == bi1 and status.loaded:
             # "Stage 1 was already executed" (sw_stage1.cpp:212-214)
-            return {"best": status.best, "bests": _crosspoints_on_disk(work), "resumed_from": bi1, "seconds": 0.0, "gcups": 0.0, "already_done": True,
+            return {"best": status.best, "bests": _crosspoints_on_disk(work), "resumed_from": bi1, "seconds": 0.0, "gcups": 0.0, "already_done": True, "reproducible_resume": False,
                     "special_rows": [r for r in part_sra.rows]}
         if last != bi0:
             # The status file is saved AFTER the row it belongs to has been renamed into place (two file writes): a kill
@@ -142,11 +143,22 @@ def stage1(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end
     status.stage = 1
     # the best strip VALUE a two-phase run left (status.mi355) only counts for the run that continues THAT partition
     key = (bi0, bj0, bi1, bj1, int(alignment_start), int(alignment_end))
-    if resumed_from is None or status.value_key != key:
-        status.value_best = None
-    status.value_key = key
+    status.claim(key, resumed_from is not None)
     prefix_value = status.value_best            # left by the run(s) this one continues: strips above row i0
+    mgr.aligner = aligner                       # (the manager asks it for the pruning state of every special row it saves)
     aligner.setSequences(v0, v1)
+    # Reproducible pruning (F_DETERMINISTIC_PRUNE): a run that continues from row i0 starts from the pruning state saved with
+    # that row and leaves the special rows of the uninterrupted run, byte for byte.  No state for exactly this row and
+    # partition, an aligner without the call, or an engine that cannot honour the state (another strip height, the int32
+    # family): the run continues as it always did -- same result, other lower bounds off the optimal paths.
+    reproducible = False
+    state = status.prune_state_for(i0) if resumed_from is not None else None
+    if state is not None and mgr.mustPruneBlocks() and hasattr(aligner, "setPruneState"):
+        try:
+            aligner.setPruneState(state["words"], state["strip_rows"], state["lag"])
+            reproducible = True
+        except AlignerError:
+            pass
     t0 = time.time()
     stop_log = _start_progress_log(aligner, mgr, progress, progress_interval, t0)
     # --max-alignments > 1: the weaker alignments are candidates too, and a pruning bound that starts from the score of the
@@ -207,5 +219,5 @@ def stage1(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end
     st = aligner.getStatistics()
     return {"best": tuple(best), "bests": [tuple(b) for b in bests], "resumed_from": resumed_from, "seconds": dt,
             "gcups": float(bi1 - i0) * (bj1 - bj0) / dt / 1e9 if dt > 0 else 0.0, "strip_rows": st["strip_rows"],
-            "kernel_ms": st["kernel_ms"], "pruned_cells": st["pruned_cells"], "located_from_value": located,
+            "kernel_ms": st["kernel_ms"], "pruned_cells": st["pruned_cells"], "located_from_value": located, "reproducible_resume": reproducible,
             "special_rows": list(part_sra.rows) if part_sra is not None else []}
