@@ -130,6 +130,15 @@ typedef struct {
                                                wavefronts later.  A stream on its own only (the bands of a chain share their finds as they arrive) */
 #define MI355SW_F_NO_GOAL_SWEEP_HEIGHTS 32768 /* mi355sw_align_partition leaves the strip height of a sweep that looks goal-stopped (MASA-Core's stages 2 and 3,
                                                see AlignJob::begin) to the cost model like any other partition's (A/B measurements) */
+#define MI355SW_F_WIDE_ALPHABET 65536       /* pairs with 15 to 62 byte values common to both sequences are coded like those with up to 14 and run on
+                                               the packed kernels -- their wide-alphabet twins (mi355sw_stats.kernel: ..._wide<...>, profile_kernel 2),
+                                               which recognise a match by the equality of two code words instead of a one-hot bit per letter -- with
+                                               everything those kernels have: block pruning of local and global alignments, the window, goal pruning,
+                                               batches, mixed strip heights, the two-phase best.  Off (the default), such a pair gets raw bytes and the
+                                               int32 kernels, as does a pair with 63 or more common byte values either way.  Read by
+                                               mi355sw_set_sequences; the results are the same bytes with the flag on and off.  Pairs with up to 14
+                                               common byte values are not affected.  MI355SW_F_FORCE_GENERIC_COMPARE wins over it; with
+                                               MI355SW_F_FORCE_INT32, and for an overflow rerun, the int32 byte-compare kernel runs on the codes */
 #define MI355SW_F_NO_HOST_COUNTER 512       /* the kernel does not mirror its strip counter into host memory (measurements) */
 #define MI355SW_V_MESSAGES 1                /* one line per noteworthy event (overflow reruns, the diagonal seed, ...) */
 #define MI355SW_V_JOBS 2                    /* timing of every mi355sw_align_partition job */
@@ -253,7 +262,7 @@ int mi355sw_align_partition(mi355sw_handle* h, const mi355sw_partition* partitio
  * mi355sw_align_partition(h, &partitions[k], managers[k], users[k]) had been called for every k -- same hooks, same
  * order PER partition, all from the calling thread -- but the partitions run side by side, so the calls of different
  * managers interleave.  Every partition needs its own manager state (borders, goal, sinks).  Partitions the batch
- * cannot take (more than 14 common byte values, >= 32 Mi rows, block pruning (other than by goal bounds) or block scores wanted, an overflow report
+ * cannot take (more than 14 common byte values -- more than 62 with MI355SW_F_WIDE_ALPHABET --, >= 32 Mi rows, block pruning (other than by goal bounds) or block scores wanted, an overflow report
  * of the packed kernel) are run one by one after the others; an overflow rerun replays what the batch attempt already
  * took and handed over (streamed first-column cells, last-column rows, special rows), as a single call's rerun does.
  * Special rows: the batch's strip height (mi355sw_config.batch_rows_per_lane) is the engine's own choice when the handle's
@@ -276,7 +285,7 @@ int mi355sw_align_partitions(mi355sw_handle* h, int32_t count, const mi355sw_par
  * other cell is its true value or a lower bound of it, and every cell at or above its bound, with every cell on a path to
  * it, is exact.  The bounds are constants, so which cells go is a function of the input.  Applies to NEEDLEMAN_WUNSCH partitions
  * with nothing tracked whose last column is dispatched, on the packed kernels at 256- / 512-row strips (rows_per_lane 4 / 8,
- * or 0: picked by the engine), in a batch at 256- / 1024-row strips; anything else -- more than 14 byte values,
+ * or 0: picked by the engine), in a batch at 256- / 1024-row strips; anything else -- more than 14 common byte values (more than 62 with MI355SW_F_WIDE_ALPHABET),
  * MI355SW_F_FORCE_INT32, an overflow rerun -- computes every cell.  No probe or seed runs and MI355SW_EBOUND does not apply
  * (the bound is not the score of a last cell).  mi355sw_stats.pruned_cells / processed_cells / kernel report it. */
 int mi355sw_set_goal_bounds(mi355sw_handle* h, int32_t count, const int32_t* column_bounds, const int32_t* row_bounds);
@@ -391,7 +400,7 @@ int mi355sw_stream_begin(mi355sw_handle* h, const mi355sw_partition* partition, 
  * gap penalties from the origin for NEEDLEMAN_WUNSCH (a global alignment).  *have_bound = 1 and *bound = the value for
  * mi355sw_stream_params.initial_bound of every band (the score of a local alignment that exists / a lower bound of the last
  * cell's score); *have_bound = 0 when there is none: an unrelated pair (local), a matrix below 64 Ki x 16 Ki, sequences the
- * packed kernel cannot take.  No stream may be active on the handle; mi355sw_stats.seed_ms of the next stream reports its time.
+ * packed kernel cannot take (63 or more common byte values, or 15 or more without MI355SW_F_WIDE_ALPHABET).  No stream may be active on the handle; mi355sw_stats.seed_ms of the next stream reports its time.
  * Reference: the bound a node starts from -- Status::load -> BestScoreList (sw_stage1.cpp:210-217) and the other nodes' best
  * score, AlignerPool::getBestNodeScore (M/common/AlignerPool.cpp:182-184). */
 int mi355sw_seed_bound(mi355sw_handle* h, const mi355sw_partition* partition, int32_t recurrence_type, int32_t* have_bound, int32_t* bound);
@@ -467,6 +476,21 @@ typedef struct { int32_t steps; double kernel_ms; int64_t dp_cells; int64_t part
 int mi355sw_stage4(mi355sw_handle* h, const mi355sw_crosspoint* in, int32_t count, int32_t max_partition_size,
                    mi355sw_crosspoint** out, int32_t* out_count, mi355sw_stage4_stats* stats);
 void mi355sw_free(void* p);
+
+/* ---- how a pair of sequences is coded for the kernels (additive in ABI 8) ------------------------------------------------
+ * What mi355sw_set_sequences does with the bytes before it uploads them.  Host code (no handle, no GPU).  `flags` =
+ * mi355sw_config.flags (MI355SW_F_FORCE_GENERIC_COMPARE and MI355SW_F_WIDE_ALPHABET are looked at).  *n_common = K, the
+ * number of byte values present in both sequences; only those can match.  *form:
+ *   0  raw bytes, the int32 byte-compare kernels: K >= 63, K >= 15 without MI355SW_F_WIDE_ALPHABET, or
+ *      MI355SW_F_FORCE_GENERIC_COMPARE; lut0 and lut1 are the identity
+ *   1  coded, K <= 14: the packed kernels with the one-hot scoring form
+ *   2  coded, 15 <= K <= 62 with MI355SW_F_WIDE_ALPHABET: the packed kernels' wide-alphabet twins
+ * Coded: lut0[b] / lut1[b] = the code of byte b in seq0 / seq1 -- the common bytes get 0..K-1 in both tables, most
+ * frequent (both sequences counted together) first, ties in byte order; a byte that is not common gets a code no byte of
+ * the other sequence carries: form 1: 7 in both tables (K <= 7), else 14 in lut0 and 15 in lut1; form 2: K in lut0 and
+ * K + 1 in lut1.  (The device holds seq0 as codes and seq1 as code * 4.) */
+int mi355sw_sequence_codes(const char* seq0, int32_t len0, const char* seq1, int32_t len1, int32_t flags, uint8_t lut0[256], uint8_t lut1[256],
+                           int32_t* n_common, int32_t* form);
 
 /* ---- stage 5: the exact alignment of every partition between consecutive crosspoints ----------------------------
  * Replaces the per-partition full-matrix traceback of MASA-Core's stage 5 (M/stage5/sw_stage5.cpp: sw() :83-319, the

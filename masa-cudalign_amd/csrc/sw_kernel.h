@@ -300,6 +300,14 @@ hipError_t launch_strip_kernel(const KernelArgs& a, KernelArgs* dargs, int rows_
 int strip_kernel_waves_per_simd(int rows_per_lane);   // int32 family: wavefronts of one launch that share a SIMD (2 for 256/512-row strips; the packed kernels: 1)
 // packed 16-bit SW kernel (sw_kernel_pk16.inc, instantiated by sw_kernel_pk16_{a..i}.hip): strip height = 128*rows_per_half
 hipError_t launch_strip_kernel_pk16(const KernelArgs& a, KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw);
+// The wide-alphabet twins of every packed launcher (sw_kernel_pk16.inc built with PK16_WIDE by sw_kernel_pk16_w{a..i}.hip:
+// the equality scoring form, up to 62 matchable codes): same arguments, same instantiations, kernels named ..._wide<...>
+hipError_t launch_strip_kernel_pk16_wide(const KernelArgs& a, KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw);
+hipError_t launch_strip_kernel_pk16_mixed_wide(const KernelArgs& a, KernelArgs* dargs, int rows_per_half_a, int rows_per_half_b, int grid,
+                                               hipStream_t stream, bool track, bool sw);
+hipError_t launch_batch_kernel_pk16_wide(const BatchArgs* dbatch, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw);
+hipError_t launch_batch_kernel_pk16_band_wide(const BatchArgs* dbatch, int grid, hipStream_t stream);
+hipError_t launch_batch_kernel_pk16_goal_wide(const BatchArgs* dbatch, int rows_per_half, int grid, hipStream_t stream);
 // stage 4 (stage4.hip): Myers-Miller refinement of a crosspoint list, batched on the GPU
 struct Stage4Crosspoint { int type, i, j, score; };          // M/common/Crosspoint.hpp
 struct Stage4Stats { int steps; double kernel_ms; long long dp_cells, partitions; };

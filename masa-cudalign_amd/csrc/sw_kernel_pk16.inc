@@ -17,6 +17,7 @@
 // constant Z^[r] = 2r - bias, and the diagonal score absorbs the shift:
 //   x = mask0[r] & mask1        one-hot base masks (bit 2+code) | bit 1, both halves at once
 //   y = pk_min_u16(x, 6)        = 6 on match, 2 otherwise        (score + 3 + 2)
+//   (PK16_WIDE, the wide-alphabet twins: x = word0[r] ^ word1 on code words (code * 4), y = 6 - pk_min_u16(x, 4) -- see below)
 //   E = sat(pk_max(TL,E) - 2)                                    (max(Hl-5,E-2) = max(Tl,E)-2, same row)
 //   g = pk_max(pk_max(diag+y, E), Z^[r])                         off the row-to-row dependency chain
 //   F = pk_max(upT, upF) ; H = pk_max(g, F) ; T = H - 3          the chain: 3 dependent ops per row
@@ -27,10 +28,43 @@
 // within a few thousand of that maximum while the 16-bit window is 65536 wide.  A per-chunk guard on the
 // chunk maximum still reports an overflow (the host then re-runs with the int32 kernel) long before a wrap
 // is possible.  -INF borders saturate at -32768 and stay there (saturating adds).
+//
+// Two scoring forms per kernel, picked per chunk: the TABLE form (one v_perm_b32 per row, wave_step16<PERM>) when every
+// column in reach carries one of the four commonest codes, else the GENERAL form above.  The one-hot general form has
+// room for 14 matchable codes (bits 2..15 of a half).  PK16_WIDE builds the same file with an EQUALITY general form
+// instead: a row's half-word is code * 4 (the pad / seq0-only code for rows that match nothing), a column's is code * 4
+// (1020 for a column outside the matrix, which no row carries), x = row ^ column is 0 exactly on equal codes and >= 4
+// otherwise, and y = 6 - pk_min_u16(x, 4) is the same 6 / 2 -- v_xor_b32, v_pk_min_u16, v_pk_sub_i16, one packed
+// instruction more than the one-hot form, for up to 62 matchable codes (code * 4 of the seq1-only code K + 1 must fit a
+// byte of seq1).  Everything else -- the table form and the test that picks it, the chunk loop, the exact replay, HALF
+// tracking, re-basing, pruning, the window, goal mode, the stop -- does not depend on how a match is recognised and is
+// shared.  The wide units (sw_kernel_pk16_w{a..i}.hip) give their kernels and launchers names of their own
+// (sw_strip_kernel_pk16_wide<...>, launch_strip_kernel_pk16_wide, ...); the units {a..i} compile this file with
+// PK16_WIDE unset and are untouched by it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sw_kernel.h"
+
+#ifndef PK16_WIDE
+#define PK16_WIDE 0
+#endif
+#if PK16_WIDE
+// the wide twins' names: every kernel and every launcher of this file
+#define sw_strip_kernel_pk16 sw_strip_kernel_pk16_wide
+#define sw_strip_kernel_pk16_mixed sw_strip_kernel_pk16_mixed_wide
+#define sw_batch_kernel_pk16 sw_batch_kernel_pk16_wide
+#define launch16_r launch16_wide_r
+#define launch_strip_kernel_pk16 launch_strip_kernel_pk16_wide
+#define launch_strip_kernel_pk16_goal launch_strip_kernel_pk16_goal_wide
+#define launch_strip_kernel_pk16_mixed launch_strip_kernel_pk16_mixed_wide
+#define launch_batch_kernel_pk16 launch_batch_kernel_pk16_wide
+#define launch_batch_kernel_pk16_r8 launch_batch_kernel_pk16_r8_wide
+#define launch_batch_kernel_pk16_band launch_batch_kernel_pk16_band_wide
+#define launch_batch_kernel_pk16_goal launch_batch_kernel_pk16_goal_wide
+// half-word of a code in the equality form (rows: code <= pad_code <= 62; columns: code <= 63, or 255 outside the matrix)
+#define WORD16(code) ((code) << 2)
+#endif
 
 namespace mi355sw {
 
@@ -194,7 +228,7 @@ struct __attribute__((aligned(16))) WaveLds16 {
     int2 out_tf[CHUNK];         // packed (T,F) words of the emit lane, one per step
     int2 dump[64];              // write-only slots of the non-emitting lanes (no EXEC toggling per step)
 #endif
-    int c1w[WIN + CHUNK + 8];   // per column j: mask(j) | mask(j-1)<<16
+    int c1w[WIN + CHUNK + 8];   // per column j: mask(j) | mask(j-1)<<16 (PK16_WIDE: the code words, same layout)
     int c1s[WIN + CHUNK + 8];   // per column j: v_perm_b32 selector {code(j), zero, 4+code(j-1), zero} (table form)
     int red[3 * 64];
 };
@@ -203,7 +237,7 @@ template <int R>
 struct Lane16 {
     s2 TL[R];       // T of the cell to the left      (lo: LO block row r, hi: HI block row r)
     s2 E[R];        // E of the cell to the left
-    int M0[R];      // one-hot base masks of the two rows
+    int M0[R];      // one-hot base masks of the two rows (PK16_WIDE: their code words)
     int TLO[R], THI[R];   // table form of the same: byte c = score of the row against column code c (c < 4)
     s2 tup_prev;    // T of (row above the block, previous column)
     s2 tbot, fbot;  // bottoms produced at the previous step
@@ -235,6 +269,9 @@ __device__ __forceinline__ void wave_step16(Lane16<R>& st, WaveLds16* lds, const
     }
     const s2 m2 = splat(-2), m3 = splat(-T_OFF);
     const us2 six = {6, 6};
+#if PK16_WIDE
+    const us2 four = {4, 4};
+#endif
     s2 t_emit = splat(0), f_emit = splat(0);
     s2 ms = splat(-32768);                                   // TRACK only: true (unshifted) maximum of the step
     s2 newT[R];
@@ -242,13 +279,18 @@ __device__ __forceinline__ void wave_step16(Lane16<R>& st, WaveLds16* lds, const
 #pragma unroll
     for (int r = 0; r < R; r++) {
         // score + 5 of the two cells: one byte permute when every column in reach is one of <= 4 plain
-        // codes (table form), else one-hot AND + min
+        // codes (table form), else one-hot AND + min (PK16_WIDE: XOR of the code words, 0 exactly on a match)
         us2 y;
         if (PERM) {
             y = __builtin_bit_cast(us2, __builtin_amdgcn_perm((u32) st.THI[r], (u32) st.TLO[r], (u32) c1p));
         } else {
+#if PK16_WIDE
+            const int x = st.M0[r] ^ c1p;
+            y = six - __builtin_elementwise_min(__builtin_bit_cast(us2, x), four);
+#else
             const int x = st.M0[r] & c1p;
             y = __builtin_elementwise_min(__builtin_bit_cast(us2, x), six);
+#endif
         }
         s2 Ev = padd_sat(pmax(st.TL[r], st.E[r]), m2);
         const s2 v = diag + __builtin_bit_cast(s2, y);
@@ -623,7 +665,11 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
         for (int half = 0; half < 2; half++) {
             const int g = (half ? lrow_hi : lrow_lo) + r;
             const int c0 = (g < a->m) ? (int) a->seq0[g] : a->pad_code;
+#if PK16_WIDE
+            mk[half] = WORD16(c0);                                     // (pad_code: the word no column carries)
+#else
             mk[half] = ((c0 < a->n_match_codes) ? (4 << c0) : 0) | 2;   // bit 1: the constant part of the score
+#endif
             tb[half] = 0x02020202 | ((c0 < a->n_match_codes && c0 < 4) ? (4 << (8 * c0)) : 0);
         }
         st.TL[r] = as_s2(pack(clamp16(h0[2 * r] - T_OFF - bias + 2 * r), clamp16(h0[2 * r + 1] - T_OFF - bias + 2 * r)));
@@ -683,8 +729,13 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
     const bool goal_any = goal_c > NEG_INF / 2 || goal_r > NEG_INF / 2;    // (a partition of a batch that brought no bound: nothing goes)
 
     // seq1 window starts empty
-    lds->c1w[lane] = 0x00020002; lds->c1w[64 + lane] = 0x00020002; lds->c1w[128 + lane] = 0x00020002;
-    if (lane < 8) lds->c1w[192 + lane] = 0x00020002;
+#if PK16_WIDE
+    constexpr int c1w_none = WORD16(255) | (WORD16(255) << 16);      // columns outside the matrix
+#else
+    constexpr int c1w_none = 0x00020002;
+#endif
+    lds->c1w[lane] = c1w_none; lds->c1w[64 + lane] = c1w_none; lds->c1w[128 + lane] = c1w_none;
+    if (lane < 8) lds->c1w[192 + lane] = c1w_none;
     lds->c1s[lane] = 0x0c040c00; lds->c1s[64 + lane] = 0x0c040c00; lds->c1s[128 + lane] = 0x0c040c00;
     if (lane < 8) lds->c1s[192 + lane] = 0x0c040c00;
     bool simple1 = false, simple2 = false;                // the previous two chunks held only plain codes (< 4)
@@ -853,8 +904,12 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
                 else ASYNC_LD32("a245", gbest_inp);
             }
             if (UNLIKELY16(trc)) q1 = __builtin_amdgcn_s_memrealtime();
+#if PK16_WIDE
+            const int mk = WORD16(code), mkp = WORD16(codep);
+#else
             const int mk = ((code < nmc) ? (4 << code) : 0) | 2;
             const int mkp = ((codep < nmc) ? (4 << codep) : 0) | 2;
+#endif
             // (local alignments: the chunks at the END of the row -- the last, partly filled one and the two in which only the
             //  trailing lanes still hold columns -- are asked too.  A strip that RETIRES (fast_forward) never computes them; one
             //  that walks the same skipped region because the strip above had not yet said "retired" used to: cells with H = 0,
@@ -1373,8 +1428,12 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
             const int cb = col0 + (count - 1) * CHUNK + lane, ca = cb - CHUNK;
             const int codeA = ld_u8_16(&seq1p[ca]) >> 2, codepA = ld_u8_16(&seq1p[ca - 1]) >> 2;
             const int codeB = ld_u8_16(&seq1p[cb]) >> 2, codepB = ld_u8_16(&seq1p[cb - 1]) >> 2;
+#if PK16_WIDE
+            const int mkA = WORD16(codeA), mkpA = WORD16(codepA), mkB = WORD16(codeB), mkpB = WORD16(codepB);
+#else
             const int mkA = ((codeA < nmc) ? (4 << codeA) : 0) | 2, mkpA = ((codepA < nmc) ? (4 << codepA) : 0) | 2;
             const int mkB = ((codeB < nmc) ? (4 << codeB) : 0) | 2, mkpB = ((codepB < nmc) ? (4 << codepB) : 0) | 2;
+#endif
             lds->c1w[64 + lane] = mkA | (mkpA << 16);
             lds->c1w[128 + lane] = mkB | (mkpB << 16);
             lds->c1s[64 + lane] = (codeA & 3) | 0x0c000c00 | ((4 + (codepA & 3)) << 16);
@@ -1415,8 +1474,12 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
             const int cb = (c - 1) * CHUNK + lane, ca = cb - CHUNK;
             const int codeA = ld_u8_16(&seq1p[ca]) >> 2, codepA = ld_u8_16(&seq1p[ca - 1]) >> 2;
             const int codeB = ld_u8_16(&seq1p[cb]) >> 2, codepB = ld_u8_16(&seq1p[cb - 1]) >> 2;
+#if PK16_WIDE
+            const int mkA = WORD16(codeA), mkpA = WORD16(codepA), mkB = WORD16(codeB), mkpB = WORD16(codepB);
+#else
             const int mkA = ((codeA < nmc) ? (4 << codeA) : 0) | 2, mkpA = ((codepA < nmc) ? (4 << codepA) : 0) | 2;
             const int mkB = ((codeB < nmc) ? (4 << codeB) : 0) | 2, mkpB = ((codepB < nmc) ? (4 << codepB) : 0) | 2;
+#endif
             lds->c1w[64 + lane] = mkA | (mkpA << 16);
             lds->c1w[128 + lane] = mkB | (mkpB << 16);
             lds->c1s[64 + lane] = (codeA & 3) | 0x0c000c00 | ((4 + (codepA & 3)) << 16);
@@ -1671,7 +1734,8 @@ __global__ void __launch_bounds__(64) sw_batch_kernel_pk16(const BatchArgs* __re
 }
 
 // One launcher per strip height and pruning mode; they are spread over six translation units
-// (sw_kernel_pk16_{a..i}.hip define PK16_PART) so that the instantiations compile in parallel.
+// (sw_kernel_pk16_{a..i}.hip define PK16_PART, sw_kernel_pk16_w{a..i}.hip PK16_WIDE as well) so that the instantiations
+// compile in parallel.
 template <int RV, bool PRUNE>
 hipError_t launch16_r(const KernelArgs* dargs, int grid, hipStream_t stream, bool track, bool sw) {
 #define LAUNCH16(TRV, SWV) hipLaunchKernelGGL((sw_strip_kernel_pk16<RV, TRV, SWV, PRUNE>), dim3(grid), dim3(64), 0, stream, dargs)

@@ -30,6 +30,7 @@ F_GENERATE_GAP_COLUMNS = 4096      # (ABI 7's opt-in; the default since ABI 8, a
 F_DETERMINISTIC_PRUNE = 16384      # reproducible special rows under block pruning
 F_NO_GOAL_SWEEP_HEIGHTS = 32768
 F_STREAM_GAP_COLUMNS = 8192        # gap-initialised first columns taken from the manager's stream instead of made on the device
+F_WIDE_ALPHABET = 65536            # pairs with 15 to 62 common byte values run on the packed kernels' wide-alphabet twins (off: int32 kernels)
 V_MESSAGES, V_JOBS, V_SEED_TILES, V_BATCH, V_DEBUG_WORDS = 1, 2, 4, 8, 16
 
 # The C library reads no environment variable (ABI 7): the MI355SW_* switches live HERE, in the Python front, and are
@@ -39,7 +40,7 @@ _ENV_FLAGS = {"MI355SW_NO_DIAGONAL_SEED": F_NO_DIAGONAL_SEED, "MI355SW_NOSEED": 
               "MI355SW_TWO_PHASE": F_TWO_PHASE, "MI355SW_NO_MIXED": F_NO_MIXED, "MI355SW_NO_SHARED_BEST": F_NO_SHARED_BEST,
               "MI355SW_NO_BATCH": F_NO_BATCH, "MI355SW_NOHOST": F_NO_HOST_COUNTER, "MI355SW_NO_WINDOW": F_NO_WINDOW, "MI355SW_STAIRCASE_SEED": F_STAIRCASE_SEED,
               "MI355SW_STREAM_GAP_COLUMNS": F_STREAM_GAP_COLUMNS, "MI355SW_DETERMINISTIC_PRUNE": F_DETERMINISTIC_PRUNE,
-              "MI355SW_NO_GOAL_SWEEP_HEIGHTS": F_NO_GOAL_SWEEP_HEIGHTS}
+              "MI355SW_NO_GOAL_SWEEP_HEIGHTS": F_NO_GOAL_SWEEP_HEIGHTS, "MI355SW_WIDE_ALPHABET": F_WIDE_ALPHABET}
 _ENV_VERBOSITY = {"MI355SW_VERBOSE": V_MESSAGES, "MI355SW_VERBOSE_JOBS": V_JOBS, "MI355SW_VERBOSE_TILES": V_SEED_TILES,
                   "MI355SW_BATCH_DEBUG": V_BATCH, "MI355SW_DEBUG": V_DEBUG_WORDS}
 
@@ -192,7 +193,7 @@ ABI_SYMBOLS = [
     "mi355sw_stream_abort", "mi355sw_stream_end", "mi355sw_stream_strip_scores",
     "mi355sw_stream_best_hint", "mi355sw_stream_running_best",
     "mi355sw_port_create", "mi355sw_port_open", "mi355sw_port_attach", "mi355sw_port_reset", "mi355sw_port_rows_ready", "mi355sw_port_read",
-    "mi355sw_port_local_pointers", "mi355sw_port_close", "mi355sw_stage4", "mi355sw_free", "mi355sw_stage5", "mi355sw_stage6_text",
+    "mi355sw_port_local_pointers", "mi355sw_port_close", "mi355sw_stage4", "mi355sw_free", "mi355sw_sequence_codes", "mi355sw_stage5", "mi355sw_stage6_text",
     "mi355sw_crosspoints_text", "mi355sw_device_count", "mi355sw_device_info",
 ]
 
@@ -281,6 +282,8 @@ def load_library():
                                    C.POINTER(Stage4Stats)]
     lib.mi355sw_free.argtypes = [C.c_void_p]
     lib.mi355sw_free.restype = None
+    lib.mi355sw_sequence_codes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.mi355sw_stage5.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                    C.POINTER(Stage5Totals), C.POINTER(C.c_int32)]
@@ -292,6 +295,20 @@ def load_library():
                                         C.POINTER(C.c_int64)]
     _lib = lib
     return lib
+
+
+def sequence_codes(data0, data1, flags=0):
+    """mi355sw_sequence_codes (host code, no GPU): how mi355sw_set_sequences would code the pair under `flags`.
+    Returns (lut0, lut1, n_common, form): two uint8 arrays of 256 codes, the number of byte values common to both sequences and
+    the form -- 0 raw bytes (int32 kernels), 1 coded one-hot (packed kernels), 2 coded wide (their wide-alphabet twins)."""
+    lib = load_library()
+    d0, d1 = _as_u8(data0), _as_u8(data1)
+    lut0, lut1 = (C.c_uint8 * 256)(), (C.c_uint8 * 256)()
+    k, form = C.c_int32(), C.c_int32()
+    rc = lib.mi355sw_sequence_codes(d0.ctypes.data, len(d0), d1.ctypes.data, len(d1), int(flags), lut0, lut1, C.byref(k), C.byref(form))
+    if rc != 0:
+        raise AlignerError("sequence_codes: %s" % ERRORS.get(rc, rc))
+    return np.frombuffer(lut0, dtype=np.uint8).copy(), np.frombuffer(lut1, dtype=np.uint8).copy(), k.value, form.value
 
 
 def stage5_events(data0, data1, crosspoints):

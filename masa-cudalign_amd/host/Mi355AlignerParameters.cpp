@@ -33,6 +33,9 @@
                            along the diagonal and start their pruning bound from the score found there;\n\
                            this option leaves that pass out (use it with --max-alignments > 1: a strong\n\
                            first bound prunes the weaker alignments away sooner).\n\
+--wide-alphabet         Sequences with 15 to 62 different letters in common (all IUPAC codes, soft-masked or\n\
+                           protein-like alphabets) run on the packed kernels too, with everything those have\n\
+                           (pruning, batches); without it they take the slower int32 kernels.  Same results.\n\
 --engine-flags=N        MI355SW_F_* switches of the engine (include/mi355sw.h), OR-ed together, decimal or 0x...:\n\
                            32 two-phase best at every size, 1024 no pruning window, 2048 staircase seed,\n\
                            4096 gap-initialised first columns made on the device, ... (the engine reads no\n\
@@ -50,6 +53,7 @@
 #define ARG_NO_DIAGONAL_SEED 0x1007
 #define ARG_ENGINE_FLAGS 0x1008
 #define ARG_ENGINE_VERBOSITY 0x1009
+#define ARG_WIDE_ALPHABET 0x100a
 
 static struct option long_options[] = {
     {"gpu",        required_argument, 0, ARG_GPU},
@@ -59,13 +63,14 @@ static struct option long_options[] = {
     {"block-columns", required_argument, 0, ARG_BLOCK_COLUMNS},
     {"prune-global", no_argument, 0, ARG_PRUNE_GLOBAL},
     {"no-diagonal-seed", no_argument, 0, ARG_NO_DIAGONAL_SEED},
+    {"wide-alphabet", no_argument, 0, ARG_WIDE_ALPHABET},
     {"engine-flags", required_argument, 0, ARG_ENGINE_FLAGS},
     {"engine-verbosity", required_argument, 0, ARG_ENGINE_VERBOSITY},
     {0, 0, 0, 0}
 };
 
 Mi355AlignerParameters::Mi355AlignerParameters() : gpu(MI355_DETECT_FASTEST_GPU), waves(0), stripRows(0), blockColumns(0), pruneGlobal(0), noDiagonalSeed(0),
-    engineFlags(0), engineVerbosity(0) {}
+    wideAlphabet(0), engineFlags(0), engineVerbosity(0) {}
 Mi355AlignerParameters::~Mi355AlignerParameters() {}
 
 void Mi355AlignerParameters::printUsage() const {
@@ -177,6 +182,9 @@ int Mi355AlignerParameters::processArgument(int argc, char** argv) {
         break;
     case ARG_NO_DIAGONAL_SEED:
         noDiagonalSeed = 1;
+        break;
+    case ARG_WIDE_ALPHABET:
+        wideAlphabet = 1;
         break;
     case ARG_ENGINE_FLAGS:              // the library reads no environment variable (ABI 7): its switches come from here
         engineFlags = (int) strtol(optarg, NULL, 0);

@@ -10,6 +10,8 @@ MI355X) behind the handful of MASA-CUDAlign options that concern the path -- not
       --max-alignments=N        trace back up to N different alignments (alignment.00.txt .. alignment.NN.txt)
       --no-block-pruning  --prune-global (block pruning for a global alignment too)  --gpu=ID  --stage-1 (best score only)
       --prune-traceback         stage 2's sweeps skip what cannot meet their goal (goal pruning; same alignment, off by default)
+      --wide-alphabet           sequences with 15 to 62 letters in common (all IUPAC codes, ...) run on the packed kernels too
+                                (MI355SW_F_WIDE_ALPHABET; same alignment, off by default)
 
 Prints one JSON line (best score, crosspoints per stage, seconds per stage) and leaves alignment.00.txt in the work
 directory.  The engine has no CPU fallback: without an MI355X this fails with MI355SW_ENOGPU."""
@@ -37,7 +39,7 @@ def main(argv):
             "+": pkg.AT_SEQUENCE_1_AND_2}
     work, limit, device, prune, only1, edges, count, ram = "./work.tmp", None, 0, True, False, "**", 1, 0
     trim, rev, comp, clear_n = [0, 0, 0, 0], [False, False], [False, False], False
-    prune_global = prune_traceback = False
+    prune_global = prune_traceback = wide_alphabet = False
     files = []
     for a in argv:
         if a.startswith("--work-dir="):
@@ -66,6 +68,8 @@ def main(argv):
             prune_global = True
         elif a == "--prune-traceback":
             prune_traceback = True
+        elif a == "--wide-alphabet":
+            wide_alphabet = True
         elif a.startswith("--gpu="):
             device = int(a[6:])
         elif a == "--stage-1":
@@ -80,7 +84,7 @@ def main(argv):
                                                          trim_start=trim[2 * k], trim_end=trim[2 * k + 1])) for k in (0, 1)]
     if limit is None:
         limit = min((len(seqs[0]) // 8192 + 2) * (len(seqs[1]) + 1) * 8, 4 << 30)
-    al = pkg.MI355Aligner(device=device)
+    al = pkg.MI355Aligner(device=device, flags=pkg.engine.F_WIDE_ALPHABET if wide_alphabet else 0)
     try:
         if only1:
             bounds = (seqs[0].offset0 - 1, seqs[1].offset0 - 1, seqs[0].offset1, seqs[1].offset1)
