@@ -35,6 +35,8 @@ namespace mi355sw {
 #define S4_GAP_FIRST 5
 #define S4_RB 4                 // rows per lane
 #define S4_PASS (64 * S4_RB)    // rows per pass
+#define S4_FOREIGN0 0xFD         // comparable byte of a seq0 byte that occurs in seq0 only (shifted codes are multiples of 4)
+#define S4_FOREIGN1 0xFF         // ... of a seq1 byte that occurs in seq1 only
 
 struct HalfProblem {
     long long a_off, b_off;     // element of row r / column c: A[a_off + r*a_stride], B[b_off + c*b_stride]
@@ -54,10 +56,20 @@ struct MatchProblem {
 
 __device__ __forceinline__ int shr1(int old, int src) { return __builtin_amdgcn_update_dpp(old, src, 0x138, 0xf, 0xf, false); }
 
-// cmp0[i] = seq0[i] << shift (coded sequences keep seq1 as code*4); afterwards equal bytes <=> matching residues
-__global__ void s4_make_comparable(const unsigned char* in, unsigned char* out, long long n, int shift) {
+// What the half-matrices compare: equal bytes <=> matching residues, as the reference's raw-byte comparison has it.
+//   coded sequences (shift 2): seq0 holds codes, seq1 holds code * 4; cmp0 = code << 2, cmp1 = code * 4.  A code at or above
+//   `n_match` stands for every byte that occurs in one sequence only -- with at most 7 common letters BOTH sequences carry the
+//   code 7 for them (the int32 nibble-profile kernel's convention) -- and such a byte never equals anything: it becomes the
+//   sentinel of its sequence (S4_FOREIGN0 / S4_FOREIGN1: odd, so no shifted code, and different from each other).
+//   raw bytes (shift 0, n_match 256): copied as they are.
+// `code_shift`: how far a byte of `in` is shifted right to give its code (0 for seq0, the shift for seq1).
+__global__ void s4_make_comparable(const unsigned char* in, unsigned char* out, long long n, int shift, int code_shift, int n_match,
+                                   int sentinel) {
     const long long stride = (long long) gridDim.x * blockDim.x;
-    for (long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) out[k] = (unsigned char) (in[k] << shift);
+    for (long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
+        const int v = in[k];
+        out[k] = (unsigned char) (((v >> code_shift) >= n_match) ? sentinel : (v << shift));
+    }
 }
 
 __global__ void __launch_bounds__(64) mm_half_kernel(const HalfProblem* __restrict__ problems, const unsigned char* __restrict__ cmp0,
@@ -201,7 +213,7 @@ int largest_partition(const std::vector<Stage4Crosspoint>& cp) {      // Crosspo
 // Returns 0, or a negative code: -1 HIP error (*hip_err), -2 a partition exceeds the reference's H_MAX, -3 a partition
 // without a matching column ("NOT FOUND" in the reference), -4 a column whose scores exceed the difference ("Error Match").
 int stage4_refine(const unsigned char* d_seq0, long long len0, const unsigned char* d_seq1, long long len1, int seq0_shift,
-                  hipStream_t stream, std::vector<Stage4Crosspoint>& list, int max_size, Stage4Stats* stats, hipError_t* hip_err) {
+                  int n_match_codes, hipStream_t stream, std::vector<Stage4Crosspoint>& list, int max_size, Stage4Stats* stats, hipError_t* hip_err) {
     static const int inv_type[] = {0, 2, 1};
     const int H_MAX = 2 * 64 * 1024;
     Buf cmp0, cmp1, d_half, d_match, d_cells;
@@ -211,8 +223,10 @@ int stage4_refine(const unsigned char* d_seq0, long long len0, const unsigned ch
     {
     S4CHK(ensure_buf(cmp0, (size_t) len0 + 64));
     S4CHK(ensure_buf(cmp1, (size_t) len1 + 64));
-    hipLaunchKernelGGL(s4_make_comparable, dim3(1024), dim3(256), 0, stream, d_seq0, (unsigned char*) cmp0.p, len0, seq0_shift);
-    hipLaunchKernelGGL(s4_make_comparable, dim3(1024), dim3(256), 0, stream, d_seq1, (unsigned char*) cmp1.p, len1, 0);
+    hipLaunchKernelGGL(s4_make_comparable, dim3(1024), dim3(256), 0, stream, d_seq0, (unsigned char*) cmp0.p, len0, seq0_shift, 0,
+                       n_match_codes, S4_FOREIGN0);
+    hipLaunchKernelGGL(s4_make_comparable, dim3(1024), dim3(256), 0, stream, d_seq1, (unsigned char*) cmp1.p, len1, 0, seq0_shift,
+                       n_match_codes, S4_FOREIGN1);
     S4CHK(hipGetLastError());
     hipEvent_t ev0, ev1;
     S4CHK(hipEventCreate(&ev0)); S4CHK(hipEventCreate(&ev1));

@@ -311,8 +311,9 @@ hipError_t launch_batch_kernel_pk16_goal_wide(const BatchArgs* dbatch, int rows_
 // stage 4 (stage4.hip): Myers-Miller refinement of a crosspoint list, batched on the GPU
 struct Stage4Crosspoint { int type, i, j, score; };          // M/common/Crosspoint.hpp
 struct Stage4Stats { int steps; double kernel_ms; long long dp_cells, partitions; };
+// n_match_codes: coded sequences' codes at or above it (bytes of one sequence only) match nothing; 256 for raw bytes
 int stage4_refine(const unsigned char* d_seq0, long long len0, const unsigned char* d_seq1, long long len1, int seq0_shift,
-                  hipStream_t stream, std::vector<Stage4Crosspoint>& list, int max_size, Stage4Stats* stats, hipError_t* hip_err);
+                  int n_match_codes, hipStream_t stream, std::vector<Stage4Crosspoint>& list, int max_size, Stage4Stats* stats, hipError_t* hip_err);
 hipError_t launch_fill_bus(int2* bus, int n, int init_type, int start_offset, hipStream_t stream);
 hipError_t launch_fill_int(int* p, long long count, int value, hipStream_t stream);
 hipError_t launch_fill_cells(int2* p, long long count, int h, int f, hipStream_t stream);

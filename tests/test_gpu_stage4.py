@@ -84,7 +84,9 @@ def test_gap_rich_alignment_has_gapped_crosspoints(pkg, oracle):
 
 @pytest.mark.parametrize("letters", [b"ACGTN", b"ACGTNRYKMSWBDHV"])
 def test_coded_and_raw_sequences(pkg, oracle, letters):
-    """the refinement compares residues like stage 1 does: coded sequences (<= 14 common letters) and raw bytes"""
+    """the refinement compares residues like stage 1 does: coded sequences (<= 14 common letters) and raw bytes.  (The base
+    letters are the first four of the GIVEN alphabet.  Letters that occur in one sequence only, in every coding form:
+    tests/test_gpu_stage4_edges.py::test_foreign_bytes_in_every_coding_form.)"""
     rng = np.random.default_rng(len(letters))
     alpha = np.frombuffer(letters, dtype=np.uint8)
     s0 = alpha[rng.integers(0, 4, 3000)].copy()
