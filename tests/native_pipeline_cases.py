@@ -30,6 +30,11 @@ CASES = {
                                   dict(sra_limit=4 * 1024 * 1024, block_pruning=True, prune_global=True, alignment_start=4, alignment_end=4), True),
     "global_unpruned_60000x50000": ("full_pipeline_global_60000x50000_b8192", dict(rows_per_lane=16),
                                     dict(sra_limit=4 * 1024 * 1024, block_pruning=False, alignment_start=4, alignment_end=4), True),
+    # the int32 kernel family under all six stages (engine.F_FORCE_INT32 = 2: the nibble-profile kernels; F_FORCE_GENERIC_COMPARE = 1:
+    # raw bytes, the byte-compare kernels -- what a pair with 15 or more common letters gets): no mid-strip stop in stages 1-3,
+    # special rows on the grid of the int32 strips, stage 4 on raw bytes
+    "int32_b8192_20000x9000": ("full_pipeline_20000x9000_b8192", dict(flags=2), dict(sra_limit=200 * 1024), True),
+    "generic_b8192_20000x9000": ("full_pipeline_20000x9000_b8192", dict(flags=1), dict(sra_limit=200 * 1024), True),
 }
 
 
@@ -45,6 +50,13 @@ def run(case_name):
     q0, q1 = fasta.parse(b">s0\n" + s0.tobytes() + b"\n"), fasta.parse(b">s1\n" + s1.tobytes() + b"\n")
     work = tempfile.mkdtemp(prefix="mi355_native_")
     al = pkg.MI355Aligner(device=0, **akw)
+    kernels = []                       # the kernel of every partition the stages hand over; the first one is stage 1's
+    single = al.alignPartition
+
+    def noted(partition, manager):
+        single(partition, manager)
+        kernels.append(al.getStatistics()["kernel"])
+    al.alignPartition = noted
     try:
         out = pipeline.align(al, q0, q1, work, **pkw)
     finally:
@@ -61,13 +73,15 @@ def run(case_name):
             af.canonical(af.loads(bytes.fromhex(case["alignment_bin_hex"])))
     else:                      # another special-row spacing may pick another, equally optimal path
         checks["start_and_end"] = bool(cp2) and cp2[0] == want2[0] and cp2[-1] == want2[-1]
+    if akw.get("flags", 0) & 3:
+        checks["int32_family"] = bool(kernels) and kernels[0].startswith("sw_strip_kernel<")
     if pkw.get("block_pruning"):
         checks["pruned"] = out["stage1"]["pruned_cells"] > 0.15 * case["m"] * case["n"]
     if "crosspoints_4" in case and exact:
         checks["crosspoints_4"] = hashlib.sha256(open(crosspoint_file(work, 4), "rb").read()).hexdigest() == case["crosspoints_4"]["file_sha256"]
     res = {"case": case_name, "checks": checks, "ok": all(checks.values()), "best": list(out["best"]),
            "crosspoints": out["crosspoints"], "seconds": out["seconds"], "stage3_rounds": out["stage3"]["rounds"],
-           "pruned_fraction": out["stage1"]["pruned_cells"] / float(case["m"]) / case["n"]}
+           "stage1_kernel": kernels[0] if kernels else None, "kernels": sorted(set(kernels)), "pruned_fraction": out["stage1"]["pruned_cells"] / float(case["m"]) / case["n"]}
     print(json.dumps(res), flush=True)
     return 0 if res["ok"] else 1
 

@@ -42,6 +42,16 @@ def test_native_pipeline_on_the_engine(name):
     assert {"best", "crosspoints_2", "alignment_txt", "alignment_score"} <= set(res["checks"])
 
 
+@pytest.mark.parametrize("name", ["int32_b8192_20000x9000", "generic_b8192_20000x9000"])
+def test_native_pipeline_on_the_int32_kernel_family(name):
+    """the same fixture with MI355SW_F_FORCE_INT32 (nibble-profile kernels) and MI355SW_F_FORCE_GENERIC_COMPARE (raw bytes, byte-compare
+    kernels: what FASTA with 15 or more common letters runs on): stage 1 runs on sw_strip_kernel<...>, and best cell, both crosspoint
+    files and the alignment, text and binary, are MASA-Core's"""
+    res = _case(name)
+    assert {"best", "crosspoints_2", "crosspoints_4", "alignment_txt", "alignment_bin", "int32_family"} <= set(res["checks"])
+    assert res["stage1_kernel"].startswith("sw_strip_kernel<"), res["kernels"]
+
+
 def test_native_pipeline_other_geometry_same_optimum():
     """against the fixture made with 128-row blocks: another spacing may pick another, equally optimal path -- score,
     start and end of the alignment are the same, and stage 5 re-scores the path to the best score"""
