@@ -290,6 +290,32 @@ int mi355sw_align_partitions(mi355sw_handle* h, int32_t count, const mi355sw_par
  * (the bound is not the score of a last cell).  mi355sw_stats.pruned_cells / processed_cells / kernel report it. */
 int mi355sw_set_goal_bounds(mi355sw_handle* h, int32_t count, const int32_t* column_bounds, const int32_t* row_bounds);
 
+/* Block pruning of an alignment that ENDS ON A SEQUENCE EDGE (additive in ABI 8): the edge for the NEXT mi355sw_stream_begin /
+ * mi355sw_align_partition, consumed by that call.  prune_blocks / must_prune_blocks of a NEEDLEMAN_WUNSCH partition means "the
+ * alignment ends in the last cell of the super-partition" (MI355SW_END_LAST_CELL, and what no call gives).  A semi-global,
+ * overlap or free-end-gap alignment ends anywhere on the last row (MI355SW_END_LAST_ROW: the whole of sequence 0 is aligned),
+ * on the last column (MI355SW_END_LAST_COLUMN) or on either (MI355SW_END_ROW_OR_COLUMN), and its score is the best H there.
+ * With the edge named, a slab of cells is skipped when nothing that enters it can still reach a running lower bound of that
+ * score: a cell that holds t with di rows and dj columns to go ends with at most t + min(di, dj) - 2 * g, where g is the gap
+ * the rest of the path is forced to hold -- max(0, di - dj) for the last row, max(0, dj - di) for the last column, 0 for
+ * either -- and proves that an alignment of at least t - 3 * min(di, dj) - (g > 0 ? 3 + 2 * g : 0) exists.  Skipped cells read
+ * -MI355SW_INF; every cell that lies on an admissible path which reaches the optimum is exact (the result cells among them),
+ * every other cell is its true value or a lower bound of it.
+ * Honoured for NEEDLEMAN_WUNSCH with nothing tracked and prune_blocks / must_prune_blocks set, the last row wanted for
+ * LAST_ROW, the last column for LAST_COLUMN, both for ROW_OR_COLUMN, on the packed kernels (one-hot or wide form) at 256-,
+ * 512-, 1024- or 2048-row strips (rows_per_lane 4 / 8 / 16 / 32, or 0: the engine picks among them).  Anything else -- another
+ * fixed height, MI355SW_F_FORCE_INT32, more than 14 common byte values without MI355SW_F_WIDE_ALPHABET, an overflow rerun, a
+ * column port, a batch, a local recurrence, a tracking manager -- computes every cell: same result, pruned_cells == 0.  A
+ * manager that dispatches the last cell keeps the last-cell rule.  initial_bound / mi355sw_stream_best_hint mean what they
+ * always do, the score of an admissible alignment that exists; the automatic seed (both extents >= 8 Mi) runs where each
+ * border is zeroes or gap penalties counted from the corner; MI355SW_EBOUND is held against the best H of the named edge(s).
+ * A value outside 0..3: MI355SW_EINVAL. */
+#define MI355SW_END_LAST_CELL 0
+#define MI355SW_END_LAST_ROW 1
+#define MI355SW_END_LAST_COLUMN 2
+#define MI355SW_END_ROW_OR_COLUMN 3
+int mi355sw_set_prune_end(mi355sw_handle* h, int32_t end);
+
 /* Pruning state of a reproducibly pruned run (MI355SW_F_DETERMINISTIC_PRUNE; additive in ABI 8): what a run that continues
  * from a special row needs to skip exactly the slabs the uninterrupted run skips below that row.
  * In that mode strip s tests against prefix[max(0, s - lag)], the bound as it stood `lag` strips above it.  The state of a

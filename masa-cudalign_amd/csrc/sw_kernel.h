@@ -114,8 +114,13 @@ struct KernelArgs {
     // -det_lag: the det_lag + 1 words in front of and at det_prefix[0] are the history the first run saved with the row this
     // stream starts from -- det_prefix[k - det_lag] = what strip k of this stream would have read had the sweep never stopped --
     // so every strip reads its own word and the clamp never acts.  The hand-over (complete_strip_common) is the same for both.
-    // (last member: the layout the kernels without pruning read stays as it was)
+    // (behind everything the kernels without pruning read: their layout stays as it was)
     int det_floor;
+    // ---- block pruning of an alignment that ends on an EDGE of the super-partition (mi355sw_set_prune_end; the EDGE
+    // instantiations of the packed pruning kernels, the only code that reads it) ----
+    // 0: the alignment ends in the last cell (the global mode); 1: anywhere on the last row; 2: anywhere on the last column;
+    // 3: on either.  gbest then holds a running lower bound of the best H on that edge.  (last member)
+    int prune_end;
 };
 
 // The argument block lives in device memory and is read through the constant address space with a
@@ -298,9 +303,9 @@ hipError_t launch_batch_kernel_pk16_goal(const BatchArgs* dbatch, int rows_per_h
 hipError_t launch_strip_kernel(const KernelArgs& a, KernelArgs* dargs, int rows_per_lane, int grid, hipStream_t stream,
                                bool sw, bool profile, bool track);
 int strip_kernel_waves_per_simd(int rows_per_lane);   // int32 family: wavefronts of one launch that share a SIMD (2 for 256/512-row strips; the packed kernels: 1)
-// packed 16-bit SW kernel (sw_kernel_pk16.inc, instantiated by sw_kernel_pk16_{a..i}.hip): strip height = 128*rows_per_half
+// packed 16-bit SW kernel (sw_kernel_pk16.inc, instantiated by sw_kernel_pk16_{a..j}.hip): strip height = 128*rows_per_half
 hipError_t launch_strip_kernel_pk16(const KernelArgs& a, KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw);
-// The wide-alphabet twins of every packed launcher (sw_kernel_pk16.inc built with PK16_WIDE by sw_kernel_pk16_w{a..i}.hip:
+// The wide-alphabet twins of every packed launcher (sw_kernel_pk16.inc built with PK16_WIDE by sw_kernel_pk16_w{a..j}.hip:
 // the equality scoring form, up to 62 matchable codes): same arguments, same instantiations, kernels named ..._wide<...>
 hipError_t launch_strip_kernel_pk16_wide(const KernelArgs& a, KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw);
 hipError_t launch_strip_kernel_pk16_mixed_wide(const KernelArgs& a, KernelArgs* dargs, int rows_per_half_a, int rows_per_half_b, int grid,

@@ -38,8 +38,8 @@
 // instruction more than the one-hot form, for up to 62 matchable codes (code * 4 of the seq1-only code K + 1 must fit a
 // byte of seq1).  Everything else -- the table form and the test that picks it, the chunk loop, the exact replay, HALF
 // tracking, re-basing, pruning, the window, goal mode, the stop -- does not depend on how a match is recognised and is
-// shared.  The wide units (sw_kernel_pk16_w{a..i}.hip) give their kernels and launchers names of their own
-// (sw_strip_kernel_pk16_wide<...>, launch_strip_kernel_pk16_wide, ...); the units {a..i} compile this file with
+// shared.  The wide units (sw_kernel_pk16_w{a..j}.hip) give their kernels and launchers names of their own
+// (sw_strip_kernel_pk16_wide<...>, launch_strip_kernel_pk16_wide, ...); the units {a..j} compile this file with
 // PK16_WIDE unset and are untouched by it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,6 +57,7 @@
 #define launch16_r launch16_wide_r
 #define launch_strip_kernel_pk16 launch_strip_kernel_pk16_wide
 #define launch_strip_kernel_pk16_goal launch_strip_kernel_pk16_goal_wide
+#define launch_strip_kernel_pk16_edge launch_strip_kernel_pk16_edge_wide
 #define launch_strip_kernel_pk16_mixed launch_strip_kernel_pk16_mixed_wide
 #define launch_batch_kernel_pk16 launch_batch_kernel_pk16_wide
 #define launch_batch_kernel_pk16_r8 launch_batch_kernel_pk16_r8_wide
@@ -548,7 +549,30 @@ __device__ __forceinline__ bool goal_keep16(const int t, const int di, const int
     return ucol >= gcol || urow >= grow;
 }
 
-template <int R, bool TRACK, bool SWF, bool PRUNE, bool GOAL = false>
+// EDGE mode of the global pruning kernels: the alignment ends on an EDGE of the super-partition instead of in its last cell --
+// KernelArgs::prune_end 1: anywhere on the last row, 2: anywhere on the last column, 3: on either -- and the result is the best
+// H there.  Everything is the global mode's (the running lower bound in gbest, det_prefix, the window, -INF for skipped cells)
+// except the gap that the rest of a path is forced to hold, g: the global mode must reach the corner, |dj - di| cells of gap;
+// a path that may end anywhere on the last row only has to get DOWN, g = max(0, di - dj); one that may end anywhere on the last
+// column only has to get ACROSS, g = max(0, dj - di); one that may do either is never forced into a gap.
+// Upper bound, as nw_upper16: every one of the min(di, dj) diagonal steps a match, the forced gap at its extension price.
+__device__ __forceinline__ int edge_upper16(const int end, const int t, const int di, const int dj, const int si, const int sj) {
+    if (t <= NEG_INF / 2) return NEG_INF - 1;             // nothing enters here: below every lower bound, known or not
+    const int inc = min(di, dj);
+    const int dlo = dj - sj - di, dhi = dj - di + si;      // range of (columns left - rows left) over the cells
+    int gmin = end == 1 ? max(0, -dhi) : (end == 2 ? max(0, dlo) : 0);   // the least forced gap among them
+    gmin = min(gmin, 400000000);                          // (int32 headroom; a weaker bound, never a wrong one)
+    return t + inc - 2 * gmin + NW_PRUNE_MARGIN;
+}
+// Lower bound, as nw_lower16: mismatches down the diagonal to the nearer edge, at most `kmax` steps, and -- only where that
+// edge is not one the alignment may end on -- one gap along it; dlo .. dhi: range of (columns left - rows left) over the cells.
+__device__ __forceinline__ int edge_lower16(const int end, const int t, const long long kmax, const long long dlo, const long long dhi) {
+    const long long gmax = end == 1 ? -dlo : (end == 2 ? dhi : 0);   // the largest forced gap among them
+    const long long lb = (long long) t - 3 * kmax - (gmax > 0 ? 3 + 2 * gmax : 0);
+    return lb > (long long) NEG_INF ? (int) lb : NEG_INF;
+}
+
+template <int R, bool TRACK, bool SWF, bool PRUNE, bool GOAL = false, bool EDGE = false>
 __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, const int s_in, WaveLds16* lds, const int lane) {
     const UniformArgs a = uniform_args(ap);
     const int s = __builtin_amdgcn_readfirstlane(s_in);
@@ -727,6 +751,8 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
     const long long gcol = goal_c <= NEG_INF / 2 ? 0x7fffffffffffffffll : (long long) goal_c;
     const long long grow = goal_r <= NEG_INF / 2 ? 0x7fffffffffffffffll : (long long) goal_r;
     const bool goal_any = goal_c > NEG_INF / 2 || goal_r > NEG_INF / 2;    // (a partition of a batch that brought no bound: nothing goes)
+    static_assert(!EDGE || (PRUNE && !SWF && !TRACK && !GOAL), "edge mode: global recurrence, pruning kernels, nothing tracked, no goal");
+    const int prune_end = EDGE ? pin32_16(a->prune_end) : 0;   // edge mode: which edge(s) the alignment may end on (see edge_upper16)
 
     // seq1 window starts empty
 #if PK16_WIDE
@@ -929,8 +955,10 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
                 } else {
                     // what enters the slab: the lane's own last column (rows of its two blocks, columns col0 - 2 lane - 4 ..
                     // + 1 with room to spare) and the bus cell of its column (row above the strip)
-                    const int own = nw_upper16(lane_entry, pr_rows - 2 * lane * R, pr_cols - col0 + 2 * lane + 4, 2 * R - 1, 5);
-                    const int top = nw_upper16(col < n ? hf.x - T_OFF : NEG_INF, pr_rows + 1, pr_cols - col + 1, 0, 1);
+                    const int own = EDGE ? edge_upper16(prune_end, lane_entry, pr_rows - 2 * lane * R, pr_cols - col0 + 2 * lane + 4, 2 * R - 1, 5)
+                                         : nw_upper16(lane_entry, pr_rows - 2 * lane * R, pr_cols - col0 + 2 * lane + 4, 2 * R - 1, 5);
+                    const int top = EDGE ? edge_upper16(prune_end, col < n ? hf.x - T_OFF : NEG_INF, pr_rows + 1, pr_cols - col + 1, 0, 1)
+                                         : nw_upper16(col < n ? hf.x - T_OFF : NEG_INF, pr_rows + 1, pr_cols - col + 1, 0, 1);
                     skip = !__any(max(own, top) >= gseen);
                 }
             }
@@ -1182,7 +1210,7 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
             if (prune_nw && !GOAL && !skip && !masked && nvalid_lo == R && nvalid_hi == R) {   // (goal mode: the bound is fixed)
                 const long long ki = (long long) pr_rows - 2 * lane * R, dj = (long long) pr_cols - col0 + 2 * lane + 1;
                 const long long dhi = dj - (ki - (2 * R - 1)), dlo = (dj - 64) - ki;
-                lbv = nw_lower16(cmv + bias, ki < dj ? ki : dj, dhi > -dlo ? dhi : -dlo);
+                lbv = EDGE ? edge_lower16(prune_end, cmv + bias, ki < dj ? ki : dj, dlo, dhi) : nw_lower16(cmv + bias, ki < dj ? ki : dj, dhi > -dlo ? dhi : -dlo);
             }
             // the wave-wide maximum (six cross-lane steps) is only needed when one of its three consumers
             // can fire; three ballots decide that
@@ -1394,7 +1422,8 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
                         if (goal_any && !__any(goal_keep16(h[k] - T_OFF, pr_rows + 1, pr_cols - (col0 + k * CHUNK + lane) + 1, 0, gcol, grow))) count = k + 1;
                     } else {
                         // (the strip holds nothing: only the bus cells can bring a path in)
-                        const int top = nw_upper16(h[k] - T_OFF, pr_rows + 1, pr_cols - (col0 + k * CHUNK + lane) + 1, 0, 1);
+                        const int top = EDGE ? edge_upper16(prune_end, h[k] - T_OFF, pr_rows + 1, pr_cols - (col0 + k * CHUNK + lane) + 1, 0, 1)
+                                             : nw_upper16(h[k] - T_OFF, pr_rows + 1, pr_cols - (col0 + k * CHUNK + lane) + 1, 0, 1);
                         if (!__any(top >= gs)) count = k + 1;
                     }
                 }
@@ -1639,7 +1668,7 @@ __device__ __attribute__((noinline)) void process_strip16(const KernelArgs* ap, 
     }
 }
 
-template <int R, bool TRACK, bool SWF, bool PRUNE, bool GOAL = false>
+template <int R, bool TRACK, bool SWF, bool PRUNE, bool GOAL = false, bool EDGE = false>
 __global__ void __launch_bounds__(64) sw_strip_kernel_pk16(const KernelArgs* __restrict__ ap) {
     __shared__ WaveLds16 lds_store;
     WaveLds16* lds = &lds_store;
@@ -1663,7 +1692,7 @@ __global__ void __launch_bounds__(64) sw_strip_kernel_pk16(const KernelArgs* __r
             __builtin_amdgcn_wave_barrier();
             break;
         } else {
-            process_strip16<R, TRACK, SWF, PRUNE, GOAL>(ap, s, lds, lane);
+            process_strip16<R, TRACK, SWF, PRUNE, GOAL, EDGE>(ap, s, lds, lane);
         }
         complete_strip_common(ap, s, lane, 128 * R, true);
     }
@@ -1734,7 +1763,7 @@ __global__ void __launch_bounds__(64) sw_batch_kernel_pk16(const BatchArgs* __re
 }
 
 // One launcher per strip height and pruning mode; they are spread over six translation units
-// (sw_kernel_pk16_{a..i}.hip define PK16_PART, sw_kernel_pk16_w{a..i}.hip PK16_WIDE as well) so that the instantiations
+// (sw_kernel_pk16_{a..j}.hip define PK16_PART, sw_kernel_pk16_w{a..j}.hip PK16_WIDE as well) so that the instantiations
 // compile in parallel.
 template <int RV, bool PRUNE>
 hipError_t launch16_r(const KernelArgs* dargs, int grid, hipStream_t stream, bool track, bool sw) {
@@ -1755,6 +1784,7 @@ PK16_DECL(2, true, extern) PK16_DECL(4, true, extern) PK16_DECL(6, true, extern)
 PK16_DECL(12, true, extern) PK16_DECL(16, true, extern)
 
 hipError_t launch_strip_kernel_pk16_goal(const KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream);   // (unit i)
+hipError_t launch_strip_kernel_pk16_edge(const KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream);   // (unit j)
 hipError_t launch_strip_kernel_pk16(const KernelArgs& a, KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw) {
     hipError_t e = hipMemcpyAsync(dargs, &a, sizeof(KernelArgs), hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) return e;
@@ -1765,6 +1795,11 @@ hipError_t launch_strip_kernel_pk16(const KernelArgs& a, KernelArgs* dargs, int 
     if (pr && (a.goal_bound_col > NEG_INF / 2 || a.goal_bound_row > NEG_INF / 2)) {
         if (track || sw) return hipErrorInvalidValue;
         return launch_strip_kernel_pk16_goal(dargs, rows_per_half, grid, stream);
+    }
+    // edge mode (unit j): the alignment ends on an edge of the super-partition, KernelArgs::prune_end says which
+    if (pr && a.prune_end != 0) {
+        if (track || sw) return hipErrorInvalidValue;
+        return launch_strip_kernel_pk16_edge(dargs, rows_per_half, grid, stream);
     }
 #define PK16_CASE(RV) case RV: return pr ? launch16_r<RV, true>(dargs, grid, stream, track, sw) : launch16_r<RV, false>(dargs, grid, stream, track, sw);
     switch (rows_per_half) {
@@ -1828,6 +1863,18 @@ hipError_t launch_batch_kernel_pk16_goal(const BatchArgs* dbatch, int rows_per_h
     if (rows_per_half == 2) hipLaunchKernelGGL((sw_batch_kernel_pk16<2, false, false, true, true>), dim3(grid), dim3(64), 0, stream, dbatch);
     else if (rows_per_half == 8) hipLaunchKernelGGL((sw_batch_kernel_pk16<8, false, false, true, true>), dim3(grid), dim3(64), 0, stream, dbatch);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+#elif PK16_PART == 9
+// edge mode (process_strip16<.., EDGE>): 256-, 512-, 1024- and 2048-row strips; global recurrence, nothing tracked, pruning kernels
+hipError_t launch_strip_kernel_pk16_edge(const KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream) {
+#define EDGE16(RV) hipLaunchKernelGGL((sw_strip_kernel_pk16<RV, false, false, true, false, true>), dim3(grid), dim3(64), 0, stream, dargs)
+    if (rows_per_half == 2) EDGE16(2);
+    else if (rows_per_half == 4) EDGE16(4);
+    else if (rows_per_half == 8) EDGE16(8);
+    else if (rows_per_half == 16) EDGE16(16);
+    else return hipErrorInvalidValue;
+#undef EDGE16
     return hipGetLastError();
 }
 #elif PK16_PART == 1

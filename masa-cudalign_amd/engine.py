@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("MI355SW_LIB") or os.path.join(HERE, "libmi355sw.so")
 INCLUDE_PATH = os.path.join(os.path.dirname(HERE), "include", "mi355sw.h")
 
 INF = 999999999
+# mi355sw_set_prune_end (MI355SW_END_*): where a pruned NEEDLEMAN_WUNSCH partition's alignment ends
+END_LAST_CELL, END_LAST_ROW, END_LAST_COLUMN, END_ROW_OR_COLUMN = 0, 1, 2, 3
 NEEDLEMAN_WUNSCH, SMITH_WATERMAN = 0, 1
 INIT_WITH_ZEROES, INIT_WITH_GAPS, INIT_WITH_CUSTOM_DATA, INIT_WITH_GAPS_OPENED = 0, 1, 2, 3
 
@@ -184,7 +186,7 @@ class ManagerTable(C.Structure):
 ABI_SYMBOLS = [
     "mi355sw_create", "mi355sw_configure", "mi355sw_destroy", "mi355sw_last_error", "mi355sw_abi_version", "mi355sw_build_id",
     "mi355sw_get_capabilities", "mi355sw_get_score_parameters", "mi355sw_set_rows_per_lane",
-    "mi355sw_set_sequences", "mi355sw_unset_sequences", "mi355sw_align_partition", "mi355sw_align_partitions", "mi355sw_set_goal_bounds",
+    "mi355sw_set_sequences", "mi355sw_unset_sequences", "mi355sw_align_partition", "mi355sw_align_partitions", "mi355sw_set_goal_bounds", "mi355sw_set_prune_end",
     "mi355sw_get_prune_state", "mi355sw_set_prune_state",
     "mi355sw_process_block", "mi355sw_match_last_column", "mi355sw_progress",
     "mi355sw_processed_cells", "mi355sw_get_stats",
@@ -249,6 +251,7 @@ def load_library():
     lib.mi355sw_align_partition.argtypes = [H, C.POINTER(Partition), C.POINTER(ManagerTable), C.c_void_p]
     lib.mi355sw_align_partitions.argtypes = [H, C.c_int32, C.POINTER(Partition), C.POINTER(C.POINTER(ManagerTable)), C.POINTER(C.c_void_p)]
     lib.mi355sw_set_goal_bounds.argtypes = [H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mi355sw_set_prune_end.argtypes = [H, C.c_int32]
     lib.mi355sw_get_prune_state.argtypes = [H, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.mi355sw_set_prune_state.argtypes = [H, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32]
     lib.mi355sw_process_block.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -528,6 +531,12 @@ class MI355Aligner:
         assert len(rows) == len(cols)
         n = len(cols)
         self._check(self._lib.mi355sw_set_goal_bounds(self._h, n, (C.c_int32 * n)(*cols), (C.c_int32 * n)(*rows)), "setGoalBounds")
+
+    def setPruneEnd(self, mode):
+        """mi355sw_set_prune_end: the NEXT alignPartition / streamBegin prunes a NEEDLEMAN_WUNSCH partition against the best
+        score of the edge its alignment ends on -- END_LAST_ROW, END_LAST_COLUMN, END_ROW_OR_COLUMN; END_LAST_CELL (0) is what
+        no call gives -- consumed by that call.  Where the edge kernels do not apply the run computes every cell."""
+        self._check(self._lib.mi355sw_set_prune_end(self._h, int(mode)), "setPruneEnd")
 
     def pruneState(self, row):
         """mi355sw_get_prune_state: the pruning state of the special row `row` (the coordinate dispatchRow is given) of a

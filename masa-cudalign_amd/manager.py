@@ -245,7 +245,7 @@ class Stage1Manager:
     def __init__(self, partition, alignment_start=AT_ANYWHERE, alignment_end=AT_ANYWHERE,
                  special_row_interval=0, keep_last_row=False, keep_last_column=False,
                  first_row_reader=None, first_column_reader=None, seq0_offset=0, seq1_offset=0,
-                 super_partition=None, block_pruning=False, sra_partition=None, status=None, max_alignments=1, prune_global=True):
+                 super_partition=None, block_pruning=False, sra_partition=None, status=None, max_alignments=1, prune_global=True, prune_edges=False):
         self.partition = partition
         self.super_partition = super_partition or partition
         self.seq0_offset, self.seq1_offset = seq0_offset, seq1_offset
@@ -277,7 +277,12 @@ class Stage1Manager:
         # (prune_global=False: the reference's own rule only -- what stage1.py / pipeline.py / tools/align_fasta.py pass unless
         #  asked otherwise, like the adapter's --prune-global: a pruned global stage 1 leaves lower bounds in its special rows,
         #  a work directory that is no longer value-compatible with one the reference wrote)
-        self.block_pruning = block_pruning and (alignment_end == AT_ANYWHERE or
+        # (prune_edges: ... and for alignments that end on a sequence edge -- semi-global, overlap, free end gaps: a global
+        #  recurrence whose result is the best score of the last row, the last column or both.  The engine has to be told which,
+        #  pruneEnd() / MI355Aligner.setPruneEnd: mustDispatchLastRow() is also true for a manager that merely saves the row.)
+        self.prune_edges = bool(prune_edges and block_pruning and alignment_start != AT_ANYWHERE and
+                                alignment_end in (AT_SEQUENCE_1, AT_SEQUENCE_2, AT_SEQUENCE_1_OR_2))
+        self.block_pruning = block_pruning and (alignment_end == AT_ANYWHERE or self.prune_edges or
                                                 (prune_global and alignment_start == AT_SEQUENCE_1_AND_2 and alignment_end == AT_SEQUENCE_1_AND_2))
         # special rows / last row go to disk when a SpecialRowsPartition is given (AlignerManager::dispatchRow ->
         # SpecialRowsPartition::write, AlignerManager.cpp:334-356); the status file follows every completed row
@@ -400,6 +405,13 @@ class Stage1Manager:
 
     def mustPruneBlocks(self):
         return self.block_pruning
+
+    def pruneEnd(self):
+        """what MI355Aligner.setPruneEnd must hear before this manager's partition runs (engine.END_*): the edge the best
+        score is read from when the manager asks for pruning on its account (prune_edges), else 0"""
+        if not self.prune_edges:
+            return 0
+        return {AT_SEQUENCE_1: 1, AT_SEQUENCE_2: 2, AT_SEQUENCE_1_OR_2: 3}[self.best_location]
 
     # --- results ---
     def getBestScore(self):

@@ -54,13 +54,15 @@ def check_work_directory(work, seq0, seq1):
 @sra_mod.with_async_files
 def align(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end=AT_ANYWHERE, sra_limit=0,
           block_pruning=True, max_partition_size=16, progress=None, max_alignments=1, ram_limit=0, prune_global=False,
-          prune_traceback=False):
+          prune_traceback=False, prune_edges=False):
     """seq0, seq1: fasta.Sequence.  Returns {"best", "alignment": stage56.Alignment or None, "text": bytes of
     alignment.00.txt or None when nothing scored above the floor, "crosspoints": {2: n, 3: n, 4: n},
     "seconds": {stage: s}}; with max_alignments > 1 also "alignments": one such record per end point stage 1 kept
     (alignment.NN.txt, crosspoint_0S.NN, special_rows/stage.0S.NN: executeTraceback, libmasa.cpp:643-657).
     prune_traceback: stage 2's sweeps skip what cannot meet their goal (stage2(prune_goal=True)); the same files but
-    special_rows/stage.02.NN, whose cells off every goal path may be lower bounds"""
+    special_rows/stage.02.NN, whose cells off every goal path may be lower bounds
+    prune_edges: stage 1 of an alignment that ends on a sequence edge prunes too (stage1(prune_edges=True)); the same files but
+    special_rows/stage.01.NN, whose cells off every optimal path may be lower bounds"""
     check_work_directory(work, seq0, seq1)
     # the data the aligner compares: forward or reversed, complemented, N-cleared (fasta.py); --trim only selects the
     # part of the matrix stage 1 sweeps, every coordinate of every stage stays absolute (Sequence.cpp:117-159)
@@ -71,7 +73,7 @@ def align(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end=
     t = time.time()
     r1 = stage1(aligner, d0, d1, work, alignment_start=alignment_start, alignment_end=alignment_end, sra_limit=sra_limit,
                 block_pruning=block_pruning, bounds=bounds, progress=progress, max_alignments=max_alignments,
-                ram_limit=ram_limit, areas=areas, prune_global=prune_global)
+                ram_limit=ram_limit, areas=areas, prune_global=prune_global, prune_edges=prune_edges)
     secs[1] = time.time() - t
     out = {"best": r1["best"], "alignment": None, "text": None, "crosspoints": {}, "seconds": secs, "stage1": r1,
            "alignments": []}

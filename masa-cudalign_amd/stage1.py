@@ -67,13 +67,23 @@ def _crosspoints_on_disk(work):
     return out
 
 
+def _hand_prune_end(aligner, mgr):
+    """edge pruning: the edge the manager reads its best score from (Stage1Manager.pruneEnd) for the aligner's next call"""
+    mode = mgr.pruneEnd() if hasattr(mgr, "pruneEnd") else 0
+    if mode and hasattr(aligner, "setPruneEnd"):
+        aligner.setPruneEnd(mode)
+    return mode
+
+
 @sra_mod.with_async_files
 def stage1(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end=AT_ANYWHERE, sra_limit=0,
            block_pruning=True, manager_class=Stage1Manager, bounds=None, progress=None, progress_interval=2.0,
-           max_alignments=1, ram_limit=0, areas=None, prune_global=False):
+           max_alignments=1, ram_limit=0, areas=None, prune_global=False, prune_edges=False):
     """Runs (or resumes) stage 1 of seq0 x seq1 in work directory `work`.  `prune_global`: block pruning for a GLOBAL alignment
     too (both ends in the corners) -- beyond the reference, whose stage 1 prunes local alignments only (sw_stage1.cpp:219-225);
-    the adapter's --prune-global.  `aligner` is an MI355Aligner; create it
+    the adapter's --prune-global.  `prune_edges`: the same for an alignment that starts on a sequence edge and ends on the
+    last row, the last column or either (alignment_end 1, 2, 3) -- the aligner is told which before every call
+    (MI355Aligner.setPruneEnd); with an aligner that has no such call every cell is computed.  `aligner` is an MI355Aligner; create it
     with a fixed strip height (rows_per_lane) when the area must be resumable or shared with CUDAlign: special rows
     sit on multiples of the strip height (1024 or 2048 rows give CUDAlign's 8192-row spacing).
     `bounds` = (i0, j0, i1, j1): the part of the matrix --trim selects (Sequence::getTrimStart()-1 .. getTrimEnd(),
@@ -137,7 +147,12 @@ def stage1(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end
                         special_row_interval=interval, first_row_reader=fr, first_column_reader=fc,
                         super_partition=sup, block_pruning=block_pruning, prune_global=prune_global,
                         sra_partition=part_sra, status=status, seq0_offset=bi0, seq1_offset=bj0,
-                        **({"max_alignments": max_alignments} if max_alignments != 1 else {}))
+                        **({"max_alignments": max_alignments} if max_alignments != 1 else {}),
+                        **({"prune_edges": True} if prune_edges else {}))
+    if prune_edges and not hasattr(aligner, "setPruneEnd") and hasattr(mgr, "prune_edges") and mgr.prune_edges:
+        # nobody can tell this aligner on which edge the alignment ends: it is not asked to prune
+        mgr.prune_edges = False
+        mgr.block_pruning = False
     if status.loaded and status.best is not None and status.best[0] >= 0:
         mgr.best_list.add(*status.best)            # Status::load -> bestScoreList->add (Status.cpp:60-64)
     status.stage = 1
@@ -168,6 +183,7 @@ def stage1(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end
     if seed_off:
         aligner.setFlag(F_NO_DIAGONAL_SEED, True)
     try:
+        _hand_prune_end(aligner, mgr)
         aligner.alignPartition(rel, mgr)
     finally:
         if seed_off:
@@ -198,6 +214,7 @@ def stage1(aligner, seq0, seq1, work, alignment_start=AT_ANYWHERE, alignment_end
                              seq0_offset=bi0, seq1_offset=bj0)
         aligner.setSequences(v0, v1)
         try:
+            _hand_prune_end(aligner, mgr2)
             aligner.alignPartition(Partition(sub.i0 - bi0, 0, sub.i1 - bi0, bj1 - bj0), mgr2)
         finally:
             aligner.unsetSequences()

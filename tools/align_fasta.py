@@ -10,6 +10,8 @@ MI355X) behind the handful of MASA-CUDAlign options that concern the path -- not
       --max-alignments=N        trace back up to N different alignments (alignment.00.txt .. alignment.NN.txt)
       --no-block-pruning  --prune-global (block pruning for a global alignment too)  --gpu=ID  --stage-1 (best score only)
       --prune-traceback         stage 2's sweeps skip what cannot meet their goal (goal pruning; same alignment, off by default)
+      --prune-edges             block pruning for an alignment that starts on a sequence edge and ends on the last row, the last
+                                column or either (edges X1, X2, X3 with X not *; same alignment, off by default)
       --wide-alphabet           sequences with 15 to 62 letters in common (all IUPAC codes, ...) run on the packed kernels too
                                 (MI355SW_F_WIDE_ALPHABET; same alignment, off by default)
 
@@ -39,7 +41,7 @@ def main(argv):
             "+": pkg.AT_SEQUENCE_1_AND_2}
     work, limit, device, prune, only1, edges, count, ram = "./work.tmp", None, 0, True, False, "**", 1, 0
     trim, rev, comp, clear_n = [0, 0, 0, 0], [False, False], [False, False], False
-    prune_global = prune_traceback = wide_alphabet = False
+    prune_global = prune_traceback = wide_alphabet = prune_edges = False
     files = []
     for a in argv:
         if a.startswith("--work-dir="):
@@ -68,6 +70,8 @@ def main(argv):
             prune_global = True
         elif a == "--prune-traceback":
             prune_traceback = True
+        elif a == "--prune-edges":
+            prune_edges = True
         elif a == "--wide-alphabet":
             wide_alphabet = True
         elif a.startswith("--gpu="):
@@ -90,12 +94,13 @@ def main(argv):
             bounds = (seqs[0].offset0 - 1, seqs[1].offset0 - 1, seqs[0].offset1, seqs[1].offset1)
             r = stage1.stage1(al, seqs[0].data(), seqs[1].data(), work, alignment_start=edge[edges[0]],
                               alignment_end=edge[edges[1]], sra_limit=limit, block_pruning=prune, bounds=bounds,
-                              progress=sys.stderr, max_alignments=count, ram_limit=ram, prune_global=prune_global)
+                              progress=sys.stderr, max_alignments=count, ram_limit=ram, prune_global=prune_global,
+                              prune_edges=prune_edges)
             res = {"best": list(r["best"]), "seconds": {"1": r["seconds"]}, "gcups": r["gcups"]}
         else:
             out = pipeline.align(al, seqs[0], seqs[1], work, alignment_start=edge[edges[0]], alignment_end=edge[edges[1]],
                                  sra_limit=limit, block_pruning=prune, progress=sys.stderr, max_alignments=count, ram_limit=ram,
-                                 prune_global=prune_global, prune_traceback=prune_traceback)
+                                 prune_global=prune_global, prune_traceback=prune_traceback, prune_edges=prune_edges)
             res = {"best": list(out["best"]), "seconds": {str(k): v for k, v in out["seconds"].items()},
                    "crosspoints": {str(k): v for k, v in out["crosspoints"].items()},
                    "alignments": [os.path.join(work, "alignment.%02d.txt" % k) for k in range(len(out["alignments"]))]}
