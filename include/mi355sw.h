@@ -305,8 +305,16 @@ int mi355sw_set_goal_bounds(mi355sw_handle* h, int32_t count, const int32_t* col
  * LAST_ROW, the last column for LAST_COLUMN, both for ROW_OR_COLUMN, on the packed kernels (one-hot or wide form) at 256-,
  * 512-, 1024- or 2048-row strips (rows_per_lane 4 / 8 / 16 / 32, or 0: the engine picks among them).  Anything else -- another
  * fixed height, MI355SW_F_FORCE_INT32, more than 14 common byte values without MI355SW_F_WIDE_ALPHABET, an overflow rerun, a
- * column port, a batch, a local recurrence, a tracking manager -- computes every cell: same result, pruned_cells == 0.  A
- * manager that dispatches the last cell keeps the last-cell rule.  initial_bound / mi355sw_stream_best_hint mean what they
+ * batch, a local recurrence, a tracking manager -- computes every cell: same result, pruned_cells == 0.  A
+ * manager that dispatches the last cell keeps the last-cell rule.
+ * A BAND OF A CHAIN (first_column_port / last_column_port / share_best, or a first column the host streams in) keeps the
+ * request: di and dj are the distances to the end of the SUPER-partition (prune_rows / prune_cols), so what every band folds
+ * into the shared running best is a lower bound of the best H on the allowed edge of the whole matrix.  Every band holds a
+ * slice of the last row: LAST_ROW / ROW_OR_COLUMN need want_last_row in each of them.  The last column lies in the band whose
+ * prune_cols equals its own width: LAST_COLUMN / ROW_OR_COLUMN need want_last_column there and nothing of a band further
+ * left, whose column goes on through its port.  The result of the chain is the best of the bands' mi355sw_stream_edge_best;
+ * MI355SW_EBOUND is the driver's to hold it to (as for the last-cell rule: one band does not see the whole edge).  A saved
+ * pruning state (mi355sw_set_prune_state) stays refused with a port.  initial_bound / mi355sw_stream_best_hint mean what they
  * always do, the score of an admissible alignment that exists; the automatic seed (both extents >= 8 Mi) runs where each
  * border is zeroes or gap penalties counted from the corner; MI355SW_EBOUND is held against the best H of the named edge(s).
  * A value outside 0..3: MI355SW_EINVAL. */
@@ -439,6 +447,16 @@ int mi355sw_stream_read_column(mi355sw_handle* h, int32_t row, mi355sw_cell* cel
 /* special row k (0-based) / last row: n cells (H,F) of columns j0..j1-1, valid once its strip is done */
 int mi355sw_stream_read_special_row(mi355sw_handle* h, int32_t k, int32_t* dp_row, mi355sw_cell* cells, int32_t col, int32_t len);
 int mi355sw_stream_read_last_row(mi355sw_handle* h, mi355sw_cell* cells, int32_t col, int32_t len);
+/* (additive in ABI 8) best H on the last row (edges & 1) and/or last column (edges & 2) of the stream's partition;
+   0-based (i, j) in the whole matrix like the best of the call that ends the stream; order: score desc, i asc, j asc.
+   `edges` takes MI355SW_END_LAST_ROW / _LAST_COLUMN / _ROW_OR_COLUMN.  Valid from the moment the stream's kernel has finished
+   (the poll says so) until the stream is ended, for any stream -- pruned or not, packed or int32.  The last row is reduced
+   where it lies, on the device: one word comes back, not n cells.  The border cells H[m][0] / H[0][n] are no candidates, nor
+   is a cell that holds -MI355SW_INF (skipped by block pruning); score = -MI355SW_INF, i = j = -1 when there is no candidate.
+   MI355SW_EINVAL: edges outside 1..3, the last row without want_last_row, the last column without want_last_column (a column
+   that leaves through a port is the next band's first column, not this call's); MI355SW_ESTATE: no stream, or its kernel
+   is still running. */
+int mi355sw_stream_edge_best(mi355sw_handle* h, int32_t edges, mi355sw_score* best);
 int mi355sw_stream_abort(mi355sw_handle* h);
 /* share_best streams: `score` is the score of an alignment that exists somewhere in the super-partition (found by
  * another band, another node, a previous run) -- for a GLOBAL alignment (NEEDLEMAN_WUNSCH with prune_blocks): a lower

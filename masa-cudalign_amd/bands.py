@@ -22,7 +22,7 @@ import time
 
 import numpy as np
 
-from .engine import INF, SMITH_WATERMAN, INIT_WITH_ZEROES, INIT_WITH_CUSTOM_DATA, Partition
+from .engine import INF, SMITH_WATERMAN, NEEDLEMAN_WUNSCH, INIT_WITH_ZEROES, INIT_WITH_GAPS, INIT_WITH_CUSTOM_DATA, Partition
 
 
 def band_limits(n, weights):
@@ -94,6 +94,26 @@ def check_chain_bound(score, bound):
                            "bound, the result is void" % (int(score), int(bound)))
 
 
+def edge_seed_bound(engine, m, n, first_row_init_type, first_col_init_type):
+    """chain_seed_bound for a chain whose alignment ends on a sequence edge (prune_end 1..3): the global seed -- the score of a
+    corner-to-corner alignment under gap borders -- is admissible under every start and end form whose borders are zeroes or gap
+    penalties counted from the corner (a border of zeroes dominates one of gap penalties cell by cell, and the last cell lies
+    on both edges), so it is asked for as the global run's.  Any other border form: no seed."""
+    own = (INIT_WITH_ZEROES, INIT_WITH_GAPS)
+    if first_row_init_type not in own or first_col_init_type not in own:
+        return None
+    return chain_seed_bound(engine, m, n, NEEDLEMAN_WUNSCH, INIT_WITH_GAPS, INIT_WITH_GAPS)
+
+
+def check_prune_end(prune_end, recurrence, track_best):
+    """prune_end 1..3 (engine.END_LAST_ROW / END_LAST_COLUMN / END_ROW_OR_COLUMN): the alignment ends on an edge of the whole
+    matrix and the result is the best H there -- a global recurrence with nothing tracked"""
+    if prune_end not in (0, 1, 2, 3):
+        raise ValueError("prune_end %r is none of 0 (the last cell / the best cell), 1 (last row), 2 (last column), 3 (either)" % (prune_end,))
+    if prune_end and (recurrence != NEEDLEMAN_WUNSCH or track_best):
+        raise ValueError("prune_end=%d needs recurrence=NEEDLEMAN_WUNSCH and track_best=False" % prune_end)
+
+
 class BandRunner:
     """Runs one band of the chain on this rank.  `dist` is torch.distributed (already initialised) or an object
     with send/recv/all_gather, or None for a single band.  All ranks must call run() with the same m.
@@ -124,6 +144,7 @@ class BandRunner:
         self.inbound_crc = None      # crc32 of the inbound boundary column of the last run(digest_inbound=True)
         self.special_rows = []       # DP rows of the special rows the last run handed to its sink
         self.hints = 0               # best-score hints this band took from the others in the last run (host transport)
+        self.edge_best = None        # prune_end != 0: best (i, j, score) of the edge cells this band holds, of the last run
         self.stall_abort_s = None    # seconds without progress after which run() gives up (None: MI355SW_BAND_STALL_S, default 900)
         # Block pruning over a chain of bands needs the best of the WHOLE matrix (the reference switches pruning off
         # when it forks, libmasa.cpp:1318-1321).  Between GPUs the kernels share it through the column ports; on the
@@ -252,7 +273,7 @@ class BandRunner:
     def run(self, m, j0, j1, recurrence=SMITH_WATERMAN, track_best=True, first_row_init_type=INIT_WITH_ZEROES,
             first_col_init_type=INIT_WITH_ZEROES, poll_sleep=0.0005, want_last_row=False, before_end=None,
             force_int32=False, digest_inbound=False, special_row_interval=0, special_row_sink=None, n_total=None,
-            keep_inbound=False):
+            keep_inbound=False, prune_end=0):
         """seq1 of the engine must already hold the whole horizontal sequence (or at least [j0,j1)).
         digest_inbound: leave the crc32 of the boundary column this band received in self.inbound_crc (host transport:
         the segments as they arrive; p2p: the port's memory, read back once the band is through).
@@ -264,9 +285,17 @@ class BandRunner:
         alignment can still gain by the rows and columns left in the SUPER-partition (M3).
         keep_inbound: leave the whole boundary column this band received, corner cell first, in self.inbound_column
         ((m+1, 2) cells (H,E)) -- what the reference tees into C00000000.INIT_WITH_CUSTOM_DATA (sw_stage1.cpp:186-191);
-        8 bytes of host memory per row (2 GB at C5's 249 M rows), like the file it becomes."""
+        8 bytes of host memory per row (2 GB at C5's 249 M rows), like the file it becomes.
+        prune_end 1 / 2 / 3: the alignment ends anywhere on the last row / the last column / either of the WHOLE matrix
+        (NEEDLEMAN_WUNSCH, track_best=False).  Every band keeps its slice of the last row (bit 1) and the last band its last
+        column (bit 2); after the kernel the best of the edge cells this band holds is read where it lies (streamEdgeBest) into
+        self.edge_best, and reduce_edge_best() gives the chain's.  With prune_blocks the engine hears of the edge before
+        every streamBegin (setPruneEnd) and skips what cannot reach it; without, every cell is computed and the result is the
+        same.  The int32 restart after an overflow computes every cell too."""
         import zlib
         from .engine import AlignerError
+        check_prune_end(prune_end, recurrence, track_best)
+        self.edge_best = None
         self.inbound_crc = 0 if digest_inbound else None
         eng, dist = self.engine, self.dist
         first, last = self.rank == 0, self.rank == self.world - 1
@@ -278,10 +307,12 @@ class BandRunner:
         # local alignments prune against the chain's running best score; global ones (NEEDLEMAN_WUNSCH with nothing tracked:
         # the answer is the last cell of the last band) against a running lower bound of that cell, AbstractBlockPruning.cpp:92-109
         prune = bool(self.prune_blocks and (track_best if recurrence == SMITH_WATERMAN else not track_best))
+        edges_here = (prune_end & 1) | ((prune_end & 2) if last else 0)      # the edge cells this band holds
         kw = dict(recurrence_type=recurrence, track_best=track_best,
                   first_row_init_type=first_row_init_type, first_row_start_offset=j0,
-                  want_last_column=(not last) and not p2p, last_column_port=(not last) and p2p,
-                  want_last_row=want_last_row, force_int32=force_int32)
+                  want_last_column=((not last) and not p2p) or bool(edges_here & 2), last_column_port=(not last) and p2p,
+                  want_last_row=want_last_row or bool(prune_end & 1), force_int32=force_int32)
+        arm = (lambda: eng.setPruneEnd(prune_end)) if (prune_end and self.prune_blocks) else (lambda: None)
         if special_row_interval > 0:
             kw.update(special_row_interval=int(special_row_interval))
         if prune:
@@ -328,10 +359,14 @@ class BandRunner:
             bound = None if int(go[1]) == NO_BOUND else int(go[1])
         try:
             if first and prune and self.seed_bound and self.world > 1 and n_total is not None:
-                bound = chain_seed_bound(eng, m, n_total, recurrence, first_row_init_type, first_col_init_type)
+                if prune_end:
+                    bound = edge_seed_bound(eng, m, n_total, first_row_init_type, first_col_init_type)
+                else:
+                    bound = chain_seed_bound(eng, m, n_total, recurrence, first_row_init_type, first_col_init_type)
             if prune and bound is not None:
                 kw.update(initial_bound=bound)
             self.initial_bound = bound
+            arm()
             eng.streamBegin(part, **kw)
         except BaseException:
             if not last and dist is not None:
@@ -384,6 +419,7 @@ class BandRunner:
             kw2 = dict(kw, force_int32=True)
             if not first and not p2p:
                 kw2["first_column_resume_rows"] = fed[0]
+            arm()
             eng.streamBegin(part, **kw2)
             self.restarts += 1
             reprobe_special()
@@ -542,6 +578,8 @@ class BandRunner:
             self.inbound_crc = zlib.crc32(np.ascontiguousarray(eng.portRead(0, m), dtype=np.int32).tobytes())
         if self.inbound_column is not None and p2p:
             self.inbound_column[1:] = eng.portRead(0, m)
+        if edges_here:
+            self.edge_best = tuple(int(x) for x in eng.streamEdgeBest(edges_here))
         if before_end is not None:       # e.g. read this band's slice of the last row while the stream is open
             before_end(eng)
         bx_stop.set()                   # the exchange thread keeps answering the other bands until every band is through
@@ -554,6 +592,7 @@ class BandRunner:
                 kw2 = dict(kw, force_int32=True)
                 if not first and not p2p:
                     kw2["first_column_resume_rows"] = fed[0]
+                arm()
                 eng.streamBegin(part, **kw2)
                 self.restarts += 1
             while True:
@@ -561,6 +600,8 @@ class BandRunner:
                 if fin:
                     break
                 time.sleep(poll_sleep)
+            if edges_here:
+                self.edge_best = tuple(int(x) for x in eng.streamEdgeBest(edges_here))
             if before_end is not None:
                 before_end(eng)
             best, _ = eng.streamEnd()
@@ -583,6 +624,12 @@ class BandRunner:
             check_chain_bound(best[2], self.initial_bound)
         return best
 
+    def reduce_edge_best(self):
+        """the result of a run(prune_end=1..3) on every rank: the best cell of the allowed edge(s) of the whole matrix, the
+        canonical maximum (score desc, i asc, j asc) over the bands' edge_best -- what Stage1Manager.getBestScore() gives for
+        the same form on one partition, as a 0-based cell.  Collective.  A pruning chain is held to the bound it started from."""
+        return self.reduce_best(self.edge_best if self.edge_best is not None else (-1, -1, -INF))
+
 
 class InProcessChain:
     """The whole band chain driven by ONE host process: handle k runs band k on GPU `devices[k]`, the boundary columns
@@ -602,6 +649,7 @@ class InProcessChain:
         self.seed_bound = seed_bound       # pruning: the diagonal seed of the whole matrix first (chain_seed_bound)
         self.initial_bound = None
         self.restarts = 0
+        self.before_end = None             # before_end(k, aligner): band k is through and its stream still open (tools, tests)
         self._rows = 0
 
     def attach(self, m):
@@ -617,24 +665,35 @@ class InProcessChain:
         self._rows = m
 
     def run(self, m, limits, recurrence=SMITH_WATERMAN, first_row_init_type=INIT_WITH_ZEROES, first_col_init_type=INIT_WITH_ZEROES,
-            force_int32=False, poll_sleep=0.0005):
+            force_int32=False, poll_sleep=0.0005, prune_end=0, initial_bound=None):
         """limits = band_limits(n, weights): band k = columns [limits[k], limits[k+1]).  Returns (best, per-band statistics):
-        best = the canonical best cell of the chain (0-based), or for NEEDLEMAN_WUNSCH (m-1, n-1, H[m][n])."""
+        best = the canonical best cell of the chain (0-based), or for NEEDLEMAN_WUNSCH (m-1, n-1, H[m][n]).
+        prune_end 1 / 2 / 3 (NEEDLEMAN_WUNSCH): the alignment ends on the last row / the last column / either, and best is the
+        best cell of that edge (BandRunner.run); the int32 retry after an overflow computes every cell.
+        initial_bound: a caller's first bound of a pruning chain -- the score of an admissible alignment that exists; the
+        larger of it and the seed's is what every band starts from, and what the result is held to (check_chain_bound)."""
         from .engine import AlignerError
         als, N = self.aligners, len(self.aligners)
         n = limits[-1]
         sw = recurrence == SMITH_WATERMAN
+        check_prune_end(prune_end, recurrence, sw)
         self.attach(m)
         self.initial_bound = None
         if self.prune_blocks and self.seed_bound and N > 1:
-            self.initial_bound = chain_seed_bound(als[0], m, n, recurrence, first_row_init_type, first_col_init_type)
+            if prune_end:
+                self.initial_bound = edge_seed_bound(als[0], m, n, first_row_init_type, first_col_init_type)
+            else:
+                self.initial_bound = chain_seed_bound(als[0], m, n, recurrence, first_row_init_type, first_col_init_type)
+        if self.prune_blocks and initial_bound is not None:
+            self.initial_bound = int(initial_bound) if self.initial_bound is None else max(self.initial_bound, int(initial_bound))
         for attempt in (0, 1):
             begun = []
             try:
                 for k in range(N):                         # left to right: band k+1's kernel starts after band k's
                     kw = dict(recurrence_type=recurrence, track_best=sw, first_row_init_type=first_row_init_type,
-                              first_row_start_offset=limits[k], last_column_port=k < N - 1, want_last_row=(not sw and k == N - 1),
-                              force_int32=bool(force_int32 or attempt))
+                              first_row_start_offset=limits[k], last_column_port=k < N - 1,
+                              want_last_row=(not sw and k == N - 1) or bool(prune_end & 1),
+                              want_last_column=bool(prune_end & 2) and k == N - 1, force_int32=bool(force_int32 or attempt))
                     if self.prune_blocks:
                         kw.update(prune_blocks=True, prune_rows=m, prune_cols=n - limits[k], share_best=N > 1)
                         if self.initial_bound is not None:
@@ -646,6 +705,8 @@ class InProcessChain:
                         if first_row_init_type != INIT_WITH_ZEROES:
                             corner[0, 0] = -2 * limits[k] - (3 if first_row_init_type == 1 else 0)
                         kw.update(first_column_init_type=INIT_WITH_CUSTOM_DATA, first_column=corner, first_column_port=True)
+                    if prune_end and self.prune_blocks:
+                        als[k].setPruneEnd(prune_end)      # (the int32 retry too: the engine then drops it together with the pruning)
                     als[k].streamBegin(Partition(0, limits[k], m, limits[k + 1]), **kw)
                     begun.append(k)
                 open_ = set(range(N))
@@ -658,12 +719,17 @@ class InProcessChain:
                         time.sleep(poll_sleep)
                 bests, stats, h_last = [], [], None
                 for k in range(N):
-                    if not sw and k == N - 1:
+                    if prune_end:
+                        here = (prune_end & 1) | ((prune_end & 2) if k == N - 1 else 0)
+                        edge = als[k].streamEdgeBest(here) if here else (-1, -1, -INF)
+                    elif not sw and k == N - 1:
                         h_last = int(als[k].streamReadLastRow(col=limits[k + 1] - limits[k] - 1, length=1)[0, 0])
+                    if self.before_end is not None:
+                        self.before_end(k, als[k])
                     b, _ = als[k].streamEnd()
-                    bests.append(b)
+                    bests.append(edge if prune_end else b)
                     stats.append(als[k].getStatistics())
-                best = canonical_best(bests) if sw else (m - 1, n - 1, h_last)
+                best = canonical_best(bests) if (sw or prune_end) else (m - 1, n - 1, h_last)
                 if self.prune_blocks:
                     check_chain_bound(best[2], self.initial_bound)
                 return best, stats
@@ -695,7 +761,10 @@ def band_stage1(runner, m, j0, j1, work, sra_limit, n_total=None, recurrence=SMI
     coordinates as stage1.py's, "band_best": this band's own, as the engine reports it (0-based cell), "work":
     this band's work directory, "special_rows": DP rows written}; `crosspoints/crosspoint_01.00` of every band holds
     the chain's best (the reference: the running best relayed along the chain, sw_stage1.cpp:421-464 -- the last
-    node's file is the one that counts there)."""
+    node's file is the one that counts there).
+    prune_end=1..3 (with recurrence=NEEDLEMAN_WUNSCH, track_best=False; BandRunner.run): "best" is the chain's best cell of the
+    allowed edge(s).  With prune_blocks the special rows are lower bounds, exact on every value that can still reach that
+    best (include/mi355sw.h, mi355sw_set_prune_end)."""
     from . import sra as sra_mod
     first = runner.rank == 0
     bwork = os.path.join(work, "FORK.%02d" % runner.rank) if runner.world > 1 else work
@@ -727,7 +796,8 @@ def band_stage1(runner, m, j0, j1, work, sra_limit, n_total=None, recurrence=SMI
     if m not in runner.special_rows:              # the partition's last row: sw_stage1.cpp:203-240's completion marker
         part.write(m, np.concatenate([np.array([[lead, -INF]], dtype=np.int32), got["row"]]))
     part.close()
-    best = runner.reduce_best(band_best)
+    # (prune_end: the result lies on an edge of the whole matrix, nothing is tracked -- the chain's best is the edge's)
+    best = runner.reduce_edge_best() if run_kw.get("prune_end") else runner.reduce_best(band_best)
     if best[0] >= 0 or best[1] >= 0:
         best = (best[0] + 1, best[1] + 1, best[2])       # the engine reports the 0-based cell, the files DP coordinates
         sra_mod.write_crosspoint(sra_mod.crosspoint_path(bwork, 1, 0), best)

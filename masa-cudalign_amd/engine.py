@@ -191,7 +191,7 @@ ABI_SYMBOLS = [
     "mi355sw_process_block", "mi355sw_match_last_column", "mi355sw_progress",
     "mi355sw_processed_cells", "mi355sw_get_stats",
     "mi355sw_stream_begin", "mi355sw_seed_bound", "mi355sw_stream_feed_column", "mi355sw_stream_poll",
-    "mi355sw_stream_read_column", "mi355sw_stream_read_special_row", "mi355sw_stream_read_last_row",
+    "mi355sw_stream_read_column", "mi355sw_stream_read_special_row", "mi355sw_stream_read_last_row", "mi355sw_stream_edge_best",
     "mi355sw_stream_abort", "mi355sw_stream_end", "mi355sw_stream_strip_scores",
     "mi355sw_stream_best_hint", "mi355sw_stream_running_best",
     "mi355sw_port_create", "mi355sw_port_open", "mi355sw_port_attach", "mi355sw_port_reset", "mi355sw_port_rows_ready", "mi355sw_port_read",
@@ -268,6 +268,7 @@ def load_library():
     lib.mi355sw_stream_read_column.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32]
     lib.mi355sw_stream_read_special_row.argtypes = [H, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.c_int32]
     lib.mi355sw_stream_read_last_row.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32]
+    lib.mi355sw_stream_edge_best.argtypes = [H, C.c_int32, C.POINTER(Score)]
     lib.mi355sw_stream_abort.argtypes = [H]
     lib.mi355sw_stream_best_hint.argtypes = [H, C.c_int32]
     lib.mi355sw_stream_running_best.argtypes = [H, C.POINTER(C.c_int32)]
@@ -691,6 +692,15 @@ class MI355Aligner:
         out = np.empty((length, 2), dtype=np.int32)
         self._check(self._lib.mi355sw_stream_read_last_row(self._h, out.ctypes.data, col, length), "streamReadLastRow")
         return out
+
+    def streamEdgeBest(self, edges):
+        """mi355sw_stream_edge_best: (i, j, score) of the best H on the last row (edges & 1) and / or the last column (edges & 2)
+        of the stream's partition -- END_LAST_ROW / END_LAST_COLUMN / END_ROW_OR_COLUMN -- in whole-matrix 0-based coordinates,
+        score desc, i asc, j asc; (-1, -1, -INF) when no cell holds a value.  Between the end of the kernel (streamPoll) and
+        streamEnd; the last row is reduced on the GPU, nothing but the result is copied."""
+        s = Score()
+        self._check(self._lib.mi355sw_stream_edge_best(self._h, int(edges), C.byref(s)), "streamEdgeBest")
+        return (s.i, s.j, s.score)
 
     def streamAbort(self):
         self._check(self._lib.mi355sw_stream_abort(self._h), "streamAbort")
