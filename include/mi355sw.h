@@ -78,7 +78,16 @@ typedef struct {
                                     AbstractDiagonalAligner::flushBlockScores (X/CUDAligner.cpp:441-452,
                                     AbstractDiagonalAligner.cpp:392-403); its only consumer is --dump-blocks
                                     (AlignerManager.cpp:418-423, BlocksFile.cpp).  Costs a second sweep of the
-                                    partition, as a chain of W-column bands.  0 = off. */
+                                    partition, as a chain of W-column bands.  0 = off.
+                                    Heights: every rows_per_lane.  The grid's block height is 64 * rows_per_lane as the caller
+                                    fixed it (0: the engine picks 4, 8 or 16, mi355sw_stats.strip_rows says which) and stays
+                                    that for the whole grid, also where an overflow report (MI355SW_EOVERFLOW16) sends the main
+                                    pass or a band to the int32 kernels, which have no 768-, 1536- or 2048-row strips: such a
+                                    band is rerun at 256 (rows_per_lane 12) or 512 rows (24, 32) and the 3 or 4 strip records
+                                    of each block are merged on the host -- score descending, then i, then j ascending.
+                                    (mi355sw_stats.strip_rows then names the height of the main pass's rerun, 512 or 1024.)
+                                    Where the int32 kernels run from the start -- MI355SW_F_FORCE_INT32, an alphabet the packed
+                                    kernels do not take -- 12 is 8 and 24 / 32 are 16, for the grid as for everything else. */
     int32_t verbosity;       /* MI355SW_V_* bits: diagnostics on stderr (0 = none) */
     double wait_seconds;     /* wall-time budget of the in-kernel waits on data somebody else delivers (the host's first
                                 column, the previous band's GPU); 0 = 3600 */
@@ -470,7 +479,25 @@ int mi355sw_stream_best_hint(mi355sw_handle* h, int32_t score);
 int mi355sw_stream_running_best(mi355sw_handle* h, int32_t* score);
 /* waits for the kernel; best = canonical (max score, min i, min j), sequence-relative 0-based cell */
 int mi355sw_stream_end(mi355sw_handle* h, mi355sw_score* best, int32_t* n_special_rows);
-/* per-strip best scores of the finished stream (for dispatch_score); returns count written */
+/* Per-strip best-score records of the finished stream (what mi355sw_align_partition hands to dispatch_score); call it
+ * after mi355sw_stream_end.  Writes at most max_count records and returns how many it wrote; cells as
+ * in mi355sw_stream_end (0-based, sequence-relative).  A strip's record is the canonical cell -- score descending, then i, then
+ * j ascending -- among the cells its lanes kept, and a lane keeps a cell only if it is at least the running best of the whole
+ * stream as the strip last saw it (ties are kept).  Which strips hold a record therefore depends on the schedule.  What
+ * holds in every schedule, on every kernel family, local or global, with track_best set, no initial_bound and fewer than
+ * 16384 columns (no pass that warms the running best before the sweep):
+ *   - at most one record per strip, in ascending strip order, its i inside the strip's rows (strip s = rows
+ *     [s * strip_rows, (s + 1) * strip_rows) of the partition, mi355sw_stats.strip_rows);
+ *   - every record is a true cell: its score is H at (i, j);
+ *   - the canonical maximum over the records is the `best` of mi355sw_stream_end;
+ *   - every strip whose own best score equals the stream's best has a record, and it is that strip's canonical cell.
+ * With waves = 1 (one wavefront takes the strips one after the other) only the strips above a strip -- and the strip itself,
+ * with values it has already kept -- can have raised the running best before it looks, so in addition
+ *   - every strip whose best score is at least the best of all strips above it holds exactly its own canonical cell.
+ * The int32 kernels never seed a strip from the running best: there every strip with a cell holds its own canonical cell.
+ * MI355SW_F_TWO_PHASE (and any partition of 32 Mi rows or more): exactly one record, the stream's best cell.  track_best = 0:
+ * no records.  (The block-score sweep, mi355sw_config.block_score_columns, is the mode in which EVERY strip reports its own
+ * canonical cell: its bands read a running best that stays at -INF.) */
 int mi355sw_stream_strip_scores(mi355sw_handle* h, mi355sw_score* out, int32_t max_count);
 /* ---- column ports: the boundary column of a band chain, GPU to GPU over xGMI -------------------------------
  * (and, for share_best streams, the running best score: two more words in the port's control block, one written by
