@@ -746,6 +746,62 @@ class InProcessChain:
                 self.attach(m)
 
 
+def _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_row_init_type, first_col_init_type, origin, run_kw,
+               extent=None):
+    """one band's stage 1 into the Special Rows Area of `bwork` (band_stage1 and serial_band_stage1 share it): the partition
+    directory, the special rows with their boundary cell, the last row, the markers and the tee'd boundary column.  Returns
+    (the band's own best as the engine reports it -- for a global run that ends in the last cell, prune_end 0 and nothing
+    tracked, the last band's (m-1, j1-1, H[m][j1]) and nothing for the others --, the partition, the DP rows written).
+    origin = (i, j): the cell of the whole matrix the chain's (0, 0) is (a --trim: the files keep absolute coordinates)."""
+    from . import sra as sra_mod
+    first, last = runner.rank == 0, runner.rank == runner.world - 1
+    oi, oj = origin
+    os.makedirs(bwork, exist_ok=True)
+    # (the spacing follows the sizes of the whole, untrimmed matrix: Job.cpp:62-67)
+    em, en = extent if extent is not None else (m, n_total if n_total is not None else j1)
+    interval = sra_mod.flush_interval(em, en, sra_limit) if sra_limit > 0 else 0
+    area = sra_mod.SpecialRowsArea(sra_mod.special_rows_path(bwork, 1, 0), disk_limit=max(sra_limit, 1))
+    part = area.create_partition(oi, oj + j0, oi + m, oj + j1)
+    part.set_border_markers(first_row_init_type, j0, first_col_init_type if first else INIT_WITH_CUSTOM_DATA, 0)
+
+    def sink(dp, c0, cells):
+        part.write(oi + dp, np.concatenate([np.asarray(c0, dtype=np.int32).reshape(1, 2), cells]))
+
+    got = {}
+    run_kw = dict(run_kw)
+    prev_end = run_kw.pop("before_end", None)
+
+    def before_end(eng):
+        got["row"] = eng.streamReadLastRow()
+        if prev_end is not None:
+            prev_end(eng)
+    band_best = runner.run(m, j0, j1, recurrence=recurrence, first_row_init_type=first_row_init_type,
+                           first_col_init_type=first_col_init_type, special_row_interval=interval,
+                           special_row_sink=sink if interval > 0 else None, n_total=n_total, want_last_row=True,
+                           before_end=before_end, keep_inbound=not first, **run_kw)
+    if first:
+        lead = 0 if first_col_init_type == INIT_WITH_ZEROES else -2 * m - (3 if first_col_init_type == 1 else 0)
+    else:
+        lead = int(runner.inbound_column[m, 0])
+        runner.inbound_column.tofile(os.path.join(part.path, "C00000000.INIT_WITH_CUSTOM_DATA"))
+    if m not in runner.special_rows:              # the partition's last row: sw_stage1.cpp:203-240's completion marker
+        part.write(oi + m, np.concatenate([np.array([[lead, -INF]], dtype=np.int32), got["row"]]))
+    part.close()
+    if recurrence == NEEDLEMAN_WUNSCH and not run_kw.get("prune_end") and not run_kw.get("track_best", True):
+        # both ends in the corners: the result is the last cell of the last band, read from the row just written
+        band_best = (m - 1, j1 - 1, int(got["row"][-1, 0])) if last else (-1, -1, -INF)
+    return band_best, part, list(runner.special_rows) + ([m] if m not in runner.special_rows else [])
+
+
+def _write_chain_best(bwork, best, origin=(0, 0)):
+    """`crosspoints/crosspoint_01.00` of a band: the chain's best, the engine's 0-based cell as DP coordinates of the whole matrix"""
+    from . import sra as sra_mod
+    if best[0] >= 0 or best[1] >= 0:
+        best = (best[0] + 1 + origin[0], best[1] + 1 + origin[1], best[2])
+        sra_mod.write_crosspoint(sra_mod.crosspoint_path(bwork, 1, 0), best)
+    return tuple(best)
+
+
 def band_stage1(runner, m, j0, j1, work, sra_limit, n_total=None, recurrence=SMITH_WATERMAN,
                 first_row_init_type=INIT_WITH_ZEROES, first_col_init_type=INIT_WITH_ZEROES, **run_kw):
     """Stage 1 of one band with its Special Rows Area: what a forked MASA-Core node leaves in its own work directory
@@ -764,42 +820,94 @@ def band_stage1(runner, m, j0, j1, work, sra_limit, n_total=None, recurrence=SMI
     node's file is the one that counts there).
     prune_end=1..3 (with recurrence=NEEDLEMAN_WUNSCH, track_best=False; BandRunner.run): "best" is the chain's best cell of the
     allowed edge(s).  With prune_blocks the special rows are lower bounds, exact on every value that can still reach that
-    best (include/mi355sw.h, mi355sw_set_prune_end)."""
-    from . import sra as sra_mod
-    first = runner.rank == 0
+    best (include/mi355sw.h, mi355sw_set_prune_end).
+    A global run that ends in the last cell (NEEDLEMAN_WUNSCH, track_best=False, prune_end 0): "best" is (m, n, H[m][n]), which
+    the last band reads from its last row -- what the traceback through the chain starts from (bands.band_traceback).
+    serial_band_stage1 leaves the same files with the bands run one after the other on one engine."""
     bwork = os.path.join(work, "FORK.%02d" % runner.rank) if runner.world > 1 else work
-    os.makedirs(bwork, exist_ok=True)
-    interval = sra_mod.flush_interval(m, n_total if n_total is not None else j1, sra_limit) if sra_limit > 0 else 0
-    area = sra_mod.SpecialRowsArea(sra_mod.special_rows_path(bwork, 1, 0), disk_limit=max(sra_limit, 1))
-    part = area.create_partition(0, j0, m, j1)
-    part.set_border_markers(first_row_init_type, j0, first_col_init_type if first else INIT_WITH_CUSTOM_DATA, 0)
-
-    def sink(dp, c0, cells):
-        part.write(dp, np.concatenate([np.asarray(c0, dtype=np.int32).reshape(1, 2), cells]))
-
-    got = {}
-    prev_end = run_kw.pop("before_end", None)
-
-    def before_end(eng):
-        got["row"] = eng.streamReadLastRow()
-        if prev_end is not None:
-            prev_end(eng)
-    band_best = runner.run(m, j0, j1, recurrence=recurrence, first_row_init_type=first_row_init_type,
-                           first_col_init_type=first_col_init_type, special_row_interval=interval,
-                           special_row_sink=sink if interval > 0 else None, n_total=n_total, want_last_row=True,
-                           before_end=before_end, keep_inbound=not first, **run_kw)
-    if first:
-        lead = 0 if first_col_init_type == INIT_WITH_ZEROES else -2 * m - (3 if first_col_init_type == 1 else 0)
-    else:
-        lead = int(runner.inbound_column[m, 0])
-        runner.inbound_column.tofile(os.path.join(part.path, "C00000000.INIT_WITH_CUSTOM_DATA"))
-    if m not in runner.special_rows:              # the partition's last row: sw_stage1.cpp:203-240's completion marker
-        part.write(m, np.concatenate([np.array([[lead, -INF]], dtype=np.int32), got["row"]]))
-    part.close()
+    band_best, _part, rows = _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_row_init_type,
+                                        first_col_init_type, (0, 0), run_kw)
     # (prune_end: the result lies on an edge of the whole matrix, nothing is tracked -- the chain's best is the edge's)
     best = runner.reduce_edge_best() if run_kw.get("prune_end") else runner.reduce_best(band_best)
-    if best[0] >= 0 or best[1] >= 0:
-        best = (best[0] + 1, best[1] + 1, best[2])       # the engine reports the 0-based cell, the files DP coordinates
-        sra_mod.write_crosspoint(sra_mod.crosspoint_path(bwork, 1, 0), best)
-    return {"best": tuple(best), "band_best": tuple(band_best), "work": bwork,
-            "special_rows": list(runner.special_rows) + ([m] if m not in runner.special_rows else [])}
+    best = _write_chain_best(bwork, best)
+    return {"best": tuple(best), "band_best": tuple(band_best), "work": bwork, "special_rows": rows}
+
+
+class _SerialLink:
+    """torch.distributed's send / recv between a band and the band the same process runs next: what band k sends -- its start
+    token, then its last column in row segments -- waits here until band k+1 asks for it"""
+
+    def __init__(self):
+        import collections
+        self.queue = collections.deque()
+
+    def send(self, t, dst=None):
+        self.queue.append(t.clone())
+
+    def recv(self, t, src=None):
+        t.copy_(self.queue.popleft())
+
+    def raise_bound(self, bound):
+        """the start token at the head of the queue carries what the next band's pruning starts from: never less than `bound`"""
+        if bound is not None and self.queue:
+            self.queue[0][1] = max(int(self.queue[0][1]), int(bound))
+
+
+def serial_band_stage1(engine, m, limits, work, sra_limit, n_total=None, recurrence=SMITH_WATERMAN,
+                       first_row_init_type=INIT_WITH_ZEROES, first_col_init_type=INIT_WITH_ZEROES, prune_blocks=False,
+                       seed_bound=True, segment_rows=1 << 16, origin=(0, 0), extent=None, **run_kw):
+    """The chain of band_stage1, band after band on ONE engine by one process -- the reference's `--split=N --part=1..N`
+    sequence: band k runs to its end, its last column (streamReadColumn, on the host) becomes band k+1's first column
+    (streamFeedColumn).  limits = band_limits(n, weights): band k = columns [limits[k], limits[k+1]).  Every `work`/FORK.NN
+    holds exactly what band_stage1 leaves there on rank k (with one band: `work` itself).  So a single GPU takes a matrix in
+    parts, each with its own Special Rows Area.
+    prune_blocks: every band prunes against the best of the bands before it -- the bound a band starts from is the largest score
+    the chain has found so far (a local chain; last-row cells of a prune_end chain) or the bound the chain started from, so it
+    only grows from band to band; the result is held to the first bound (check_chain_bound).  prune_end as band_stage1's.
+    origin = (i, j): where the chain's cell (0, 0) lies in the whole matrix (a --trim); directory names, rows and crosspoints
+    are absolute, `limits` and `m` relative to it; extent = (rows, columns) of the untrimmed matrix, which the spacing of the
+    special rows follows (default: m x n_total).
+    Returns {"best": the chain's best (i, j, score) in 1-based DP coordinates, "bands": [per band {"best" (its own, 0-based
+    cell), "work", "special_rows", "seconds", "pruned_cells", "initial_bound"}], "limits"}."""
+    N = len(limits) - 1
+    if N < 1 or any(limits[k] >= limits[k + 1] for k in range(N)) or limits[0] != 0:
+        raise ValueError("serial_band_stage1: limits %r are no chain of bands" % (list(limits),))
+    n_total = limits[-1] if n_total is None else n_total
+    link = _SerialLink() if N > 1 else None
+    prune_end = run_kw.get("prune_end", 0)
+    bands, cands, bound, first_bound = [], [], None, None
+    for k in range(N):
+        runner = BandRunner(engine, dist=link, rank=k, world=N, segment_rows=segment_rows, prune_blocks=prune_blocks,
+                            transport="host", seed_bound=seed_bound)
+        if k > 0:
+            link.raise_bound(bound)
+        bwork = os.path.join(work, "FORK.%02d" % k) if N > 1 else work
+        t0 = time.time()
+        band_best, _part, rows = _band_area(runner, m, limits[k], limits[k + 1], bwork, sra_limit, n_total, recurrence,
+                                            first_row_init_type, first_col_init_type, origin, run_kw, extent)
+        mine = runner.edge_best if prune_end else band_best
+        mine = tuple(int(x) for x in mine) if mine is not None else (-1, -1, -INF)
+        cands.append(mine)
+        if k == 0:
+            first_bound = runner.initial_bound
+        if runner.initial_bound is not None:
+            bound = runner.initial_bound if bound is None else max(bound, runner.initial_bound)
+        # a score some alignment of the asked form reaches: a local best; a last-row cell of a chain that may end on the last row
+        if (recurrence == SMITH_WATERMAN or (prune_end & 1 and k < N - 1)) and mine[2] > -INF:
+            bound = mine[2] if bound is None else max(bound, mine[2])
+        st = engine.getStatistics() if hasattr(engine, "getStatistics") else {}
+        bands.append({"best": mine, "work": bwork, "special_rows": rows, "seconds": time.time() - t0,
+                      "pruned_cells": int(st.get("pruned_cells", 0)), "initial_bound": runner.initial_bound,
+                      "restarts": runner.restarts})
+    best = canonical_best(cands)
+    if prune_blocks:
+        check_chain_bound(best[2], first_bound)
+    for b in bands:
+        out = _write_chain_best(b["work"], best, origin)
+    return {"best": tuple(out), "bands": bands, "limits": list(limits)}
+
+
+def band_traceback(runner, seq0, seq1, work, limits, **kw):
+    """Stages 2-6 over the chain band_stage1 left, collective over the runner's ranks: band_traceback.traceback_ranks."""
+    from . import band_traceback as bt
+    return bt.traceback_ranks(runner, seq0, seq1, work, limits, **kw)

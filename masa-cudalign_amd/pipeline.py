@@ -99,20 +99,30 @@ def _traceback(aligner, seq0, seq1, d0, d1, work, ident, alignment_start, sra_li
     t = time.time()
     r3 = stage3(aligner, d0, d1, work, sra_limit=sra_limit, ident=ident, ram_limit=ram_limit, areas=areas)
     clock(3, t)
+    rec = _finish(aligner, seq0, seq1, d0, d1, work, ident, r3["crosspoints"], max_partition_size, secs)
+    rec["crosspoints"].update({2: len(r2["crosspoints"]), 3: len(r3["crosspoints"])})
+    rec.update(stage2=r2, stage3=r3)
+    return rec
+
+
+def _finish(aligner, seq0, seq1, d0, d1, work, ident, crosspoints3, max_partition_size, secs):
+    """stages 4-6 from a list of stage 3: crosspoint_04.NN, alignment.NN.bin, alignment.NN.txt in `work`"""
+    def clock(stage, t0):
+        secs[stage] = secs.get(stage, 0.0) + time.time() - t0
     t = time.time()
     aligner.setSequences(d0, d1)
     try:
         try:
-            cp4, st4 = aligner.stage4(r3["crosspoints"], max_partition_size, as_array=True)
+            cp4, st4 = aligner.stage4(crosspoints3, max_partition_size, as_array=True)
         except TypeError:              # an aligner double without the array form
-            cp4, st4 = aligner.stage4(r3["crosspoints"], max_partition_size)
+            cp4, st4 = aligner.stage4(crosspoints3, max_partition_size)
     finally:
         aligner.unsetSequences()
     # crosspoint_04: millions of points at sizes like C3 (130 MB of text, seconds of formatting).  Nothing in this run reads the
     # file back -- stage 5 takes the array -- so it is written by the areas' file thread while stages 5 and 6 run in the library
     # (their calls release the interpreter); in place when align() returns, like every queued file (sra.async_files)
     if isinstance(cp4, np.ndarray):
-        sra_mod.queue_file_operation(_traceback, save_array, crosspoint_file(work, 4, ident), cp4)
+        sra_mod.queue_file_operation(_finish, save_array, crosspoint_file(work, 4, ident), cp4)
     else:
         save_array(crosspoint_file(work, 4, ident), cp4)
     clock(4, t)
@@ -126,5 +136,86 @@ def _traceback(aligner, seq0, seq1, d0, d1, work, ident, alignment_start, sra_li
     with open(os.path.join(work, "alignment.%02d.txt" % ident), "wb") as f:
         f.write(text)
     clock(6, t)
-    return dict(alignment=al, text=text, crosspoints={2: len(r2["crosspoints"]), 3: len(r3["crosspoints"]), 4: len(cp4)},
-                stage2=r2, stage3=r3, stage4=st4)
+    return dict(alignment=al, text=text, crosspoints={4: len(cp4)}, stage4=st4)
+
+
+def chain_form(alignment_start, alignment_end):
+    """the stage-1 set-up of a chain of bands for the alignment's edges (sw_stage1.cpp:137-161, :318-322, BandRunner.run):
+    keywords of bands.serial_band_stage1 / band_stage1"""
+    from .manager import AT_SEQUENCE_1, AT_SEQUENCE_2, AT_SEQUENCE_1_OR_2, AT_SEQUENCE_1_AND_2
+    from .engine import SMITH_WATERMAN, NEEDLEMAN_WUNSCH, INIT_WITH_ZEROES, INIT_WITH_GAPS
+    if alignment_start == AT_ANYWHERE:
+        if alignment_end != AT_ANYWHERE:
+            raise ValueError("a chain of bands runs a local start (*) with a local end (*) only")
+        return dict(recurrence=SMITH_WATERMAN, first_row_init_type=INIT_WITH_ZEROES, first_col_init_type=INIT_WITH_ZEROES)
+    Z, G = INIT_WITH_ZEROES, INIT_WITH_GAPS
+    rows = {AT_SEQUENCE_1: (Z, G), AT_SEQUENCE_2: (G, Z), AT_SEQUENCE_1_OR_2: (Z, Z), AT_SEQUENCE_1_AND_2: (G, G)}
+    ends = {AT_SEQUENCE_1: 1, AT_SEQUENCE_2: 2, AT_SEQUENCE_1_OR_2: 3, AT_SEQUENCE_1_AND_2: 0}
+    if alignment_start not in rows or alignment_end not in ends:
+        raise ValueError("a chain of bands cannot start at %r and end at %r" % (alignment_start, alignment_end))
+    return dict(recurrence=NEEDLEMAN_WUNSCH, first_row_init_type=rows[alignment_start][0], first_col_init_type=rows[alignment_start][1],
+                track_best=False, prune_end=ends[alignment_end])
+
+
+@sra_mod.with_async_files
+def align_bands(aligner, seq0, seq1, work, weights, alignment_start=AT_ANYWHERE, alignment_end=AT_ANYWHERE, sra_limit=0,
+                block_pruning=True, max_partition_size=16, progress=None, max_alignments=1, ram_limit=0, prune_global=False,
+                prune_traceback=False, prune_edges=False):
+    """align() with stage 1 taken in len(weights) column bands, one after the other on `aligner` (bands.serial_band_stage1:
+    band k gets weights[k] / sum(weights) of the columns, its own Special Rows Area in `work`/FORK.NN and `sra_limit` of
+    budget, like a --split node), and the alignment traced back through the chain (band_traceback.traceback_serial).  So one
+    GPU aligns a matrix whose special rows it could not keep in one piece, and what the ranks of a chain leave is read the
+    same way (bands.band_traceback).  Returns align()'s record plus "bands": per band its role, crosspoint counts and
+    seconds per stage (stage 1 included), and "keeper".
+    Block pruning applies where a band's stage 1 prunes: local alignments (block_pruning), global ones (prune_global),
+    alignments that end on an edge (prune_edges).  ram_limit is not split over bands: rows are kept on disk.
+    With ONE band this is align() itself: same path, same files."""
+    from . import bands as bands_mod
+    from . import band_traceback as bt
+    from .manager import AT_SEQUENCE_1_AND_2
+    if max_alignments != 1:
+        raise ValueError("max_alignments=%d: a chain of bands traces one alignment back" % max_alignments)
+    weights = [int(w) for w in weights]
+    if not weights or min(weights) <= 0:
+        raise ValueError("weights %r: one positive weight per band" % (weights,))
+    if len(weights) == 1:
+        out = align(aligner, seq0, seq1, work, alignment_start=alignment_start, alignment_end=alignment_end, sra_limit=sra_limit,
+                    block_pruning=block_pruning, max_partition_size=max_partition_size, progress=progress, ram_limit=ram_limit,
+                    prune_global=prune_global, prune_traceback=prune_traceback, prune_edges=prune_edges)
+        out["bands"] = [{"band": 0, "role": "band", "crosspoints": dict(out["crosspoints"]), "seconds": dict(out["seconds"])}]
+        out["keeper"] = 0
+        return out
+    form = chain_form(alignment_start, alignment_end)
+    check_work_directory(work, seq0, seq1)
+    d0, d1 = np.ascontiguousarray(seq0.data()), np.ascontiguousarray(seq1.data())
+    bi0, bj0, bi1, bj1 = seq0.offset0 - 1, seq1.offset0 - 1, seq0.offset1, seq1.offset1
+    rel = bands_mod.band_limits(bj1 - bj0, weights)
+    if any(rel[k] >= rel[k + 1] for k in range(len(weights))):
+        raise ValueError("weights %r leave a band of %d columns empty" % (weights, bj1 - bj0))
+    if alignment_start == AT_ANYWHERE:
+        prune = bool(block_pruning)
+    elif form["prune_end"]:
+        prune = bool(block_pruning and prune_edges)
+    else:
+        prune = bool(block_pruning and prune_global and alignment_start == AT_SEQUENCE_1_AND_2)
+    secs = {}
+    t = time.time()
+    aligner.setSequences(d0[bi0:bi1], d1[bj0:bj1])
+    try:
+        r1 = bands_mod.serial_band_stage1(aligner, bi1 - bi0, rel, work, sra_limit, prune_blocks=prune, origin=(bi0, bj0),
+                                          extent=(len(d0), len(d1)), **form)
+    finally:
+        aligner.unsetSequences()
+    secs[1] = time.time() - t
+    out = {"best": r1["best"], "alignment": None, "text": None, "crosspoints": {}, "seconds": secs, "stage1": r1, "alignments": [],
+           "bands": [{"band": k, "role": "idle", "crosspoints": {}, "seconds": {1: b["seconds"]}} for k, b in enumerate(r1["bands"])]}
+    if r1["best"][2] <= -INF or r1["best"][0] < 0:
+        return out
+    limits = [bj0 + x for x in rel]
+    rec = bt.traceback_serial(aligner, seq0, seq1, work, limits, alignment_start=alignment_start, sra_limit=sra_limit,
+                              max_partition_size=max_partition_size, prune_traceback=prune_traceback, secs=secs)
+    for b, b1 in zip(rec["bands"], r1["bands"]):
+        b["seconds"][1] = b1["seconds"]
+    out["alignments"].append(rec)
+    out.update(rec)
+    return out

@@ -12,6 +12,9 @@ MI355X) behind the handful of MASA-CUDAlign options that concern the path -- not
       --prune-traceback         stage 2's sweeps skip what cannot meet their goal (goal pruning; same alignment, off by default)
       --prune-edges             block pruning for an alignment that starts on a sequence edge and ends on the last row, the last
                                 column or either (edges X1, X2, X3 with X not *; same alignment, off by default)
+      --split=N | --split=W1,W2,...  stage 1 in N column bands of equal width (or of the given weights), one after the other on
+                                the GPU, each with its own Special Rows Area of --disk-size in <work>/FORK.NN, and the alignment
+                                traced back through the chain (pipeline.align_bands; one alignment, no --ram-size)
       --wide-alphabet           sequences with 15 to 62 letters in common (all IUPAC codes, ...) run on the packed kernels too
                                 (MI355SW_F_WIDE_ALPHABET; same alignment, off by default)
 
@@ -42,6 +45,7 @@ def main(argv):
     work, limit, device, prune, only1, edges, count, ram = "./work.tmp", None, 0, True, False, "**", 1, 0
     trim, rev, comp, clear_n = [0, 0, 0, 0], [False, False], [False, False], False
     prune_global = prune_traceback = wide_alphabet = prune_edges = False
+    weights = None
     files = []
     for a in argv:
         if a.startswith("--work-dir="):
@@ -74,6 +78,9 @@ def main(argv):
             prune_edges = True
         elif a == "--wide-alphabet":
             wide_alphabet = True
+        elif a.startswith("--split="):
+            v = [int(x) for x in a[8:].split(",")]
+            weights = [1] * v[0] if len(v) == 1 else v
         elif a.startswith("--gpu="):
             device = int(a[6:])
         elif a == "--stage-1":
@@ -97,6 +104,15 @@ def main(argv):
                               progress=sys.stderr, max_alignments=count, ram_limit=ram, prune_global=prune_global,
                               prune_edges=prune_edges)
             res = {"best": list(r["best"]), "seconds": {"1": r["seconds"]}, "gcups": r["gcups"]}
+        elif weights is not None and len(weights) > 1:
+            out = pipeline.align_bands(al, seqs[0], seqs[1], work, weights, alignment_start=edge[edges[0]], alignment_end=edge[edges[1]],
+                                       sra_limit=limit, block_pruning=prune, max_alignments=count, prune_global=prune_global,
+                                       prune_traceback=prune_traceback, prune_edges=prune_edges)
+            res = {"best": list(out["best"]), "seconds": {str(k): v for k, v in out["seconds"].items()},
+                   "crosspoints": {str(k): v for k, v in out["crosspoints"].items()}, "keeper": out.get("keeper"),
+                   "bands": [{"band": b["band"], "role": b["role"], "crosspoints": {str(k): v for k, v in b["crosspoints"].items()},
+                              "seconds": {str(k): v for k, v in b["seconds"].items()}} for b in out["bands"]],
+                   "alignments": [os.path.join(work, "alignment.00.txt")] if out["text"] is not None else []}
         else:
             out = pipeline.align(al, seqs[0], seqs[1], work, alignment_start=edge[edges[0]], alignment_end=edge[edges[1]],
                                  sra_limit=limit, block_pruning=prune, progress=sys.stderr, max_alignments=count, ram_limit=ram,
