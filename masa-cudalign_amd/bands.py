@@ -270,10 +270,34 @@ class BandRunner:
             except AlignerError:            # (a stream the check left active: the caller closes the engine)
                 self.engine._opts["wait_seconds"] = saved_wait
 
-    def run(self, m, j0, j1, recurrence=SMITH_WATERMAN, track_best=True, first_row_init_type=INIT_WITH_ZEROES,
-            first_col_init_type=INIT_WITH_ZEROES, poll_sleep=0.0005, want_last_row=False, before_end=None,
-            force_int32=False, digest_inbound=False, special_row_interval=0, special_row_sink=None, n_total=None,
-            keep_inbound=False, prune_end=0):
+    def run(self, *args, **kwargs):
+        """_run (below) with the stream cleaned up behind it: whatever ends the run once its stream has begun -- an engine error,
+        an exception out of `special_row_sink` or out of the link to the next band, a stalled chain -- the kernel is stopped
+        (streamAbort) and the stream ended before the exception travels on, so the engine takes the next streamBegin."""
+        self._stream_open = False
+        self._rx_stop = threading.Event()
+        self._bx_stop = self._rx = None
+        try:
+            return self._run(*args, **kwargs)
+        except BaseException:
+            self._rx_stop.set()
+            if self._bx_stop is not None:
+                self._bx_stop.set()
+            if self._rx is not None:            # (a receiver in the middle of a feed finishes it before the stream goes)
+                self._rx.join(timeout=5.0)
+            if self._stream_open:
+                self._stream_open = False
+                for fn in (self.engine.streamAbort, self.engine.streamEnd):
+                    try:
+                        fn()
+                    except Exception:           # (no stream any more: the path that raised has ended it already)
+                        pass
+            raise
+
+    def _run(self, m, j0, j1, recurrence=SMITH_WATERMAN, track_best=True, first_row_init_type=INIT_WITH_ZEROES,
+             first_col_init_type=INIT_WITH_ZEROES, poll_sleep=0.0005, want_last_row=False, before_end=None,
+             force_int32=False, digest_inbound=False, special_row_interval=0, special_row_sink=None, n_total=None,
+             keep_inbound=False, prune_end=0, row0=0, first_row=None, inbound_prefix=None, initial_bound=None):
         """seq1 of the engine must already hold the whole horizontal sequence (or at least [j0,j1)).
         digest_inbound: leave the crc32 of the boundary column this band received in self.inbound_crc (host transport:
         the segments as they arrive; p2p: the port's memory, read back once the band is through).
@@ -291,7 +315,15 @@ class BandRunner:
         column (bit 2); after the kernel the best of the edge cells this band holds is read where it lies (streamEdgeBest) into
         self.edge_best, and reduce_edge_best() gives the chain's.  With prune_blocks the engine hears of the edge before
         every streamBegin (setPruneEnd) and skips what cannot reach it; without, every cell is computed and the result is the
-        same.  The int32 restart after an overflow computes every cell too."""
+        same.  The int32 restart after an overflow computes every cell too.
+        row0 = r > 0 (a band that is resumed, serial_band_stage1(resume=True); host transport or a single band): the band runs
+        rows (r, m] only, as Partition(r, j0, m, j1).  first_row: the n + 1 cells (H,F) of DP row r, boundary cell first (the
+        special row as it lies on disk); inbound_prefix: cells 0..r of the inbound column, corner first (every band but the
+        first) -- its cell r is the partition's corner, and the left neighbour sends rows r.. only.  Outbound segments start
+        at row r, special rows come on the grid of the whole band and reach the sink with their row of the whole band, and
+        pruning counts m - r rows to the end of the matrix.
+        initial_bound: the bound the FIRST band's pruning starts from in place of the diagonal seed (the bound a resumed chain
+        started from); the other bands hear theirs from the left."""
         import zlib
         from .engine import AlignerError
         check_prune_end(prune_end, recurrence, track_best)
@@ -301,7 +333,12 @@ class BandRunner:
         first, last = self.rank == 0, self.rank == self.world - 1
         self.inbound_column = np.empty((m + 1, 2), dtype=np.int32) if (keep_inbound and not first) else None
         p2p = self.transport == "p2p"
-        part = Partition(0, j0, m, j1)
+        row0 = int(row0)
+        if row0:
+            if not 0 < row0 < m or first_row is None or p2p or (not first and inbound_prefix is None):
+                raise ValueError("run(row0=%d): a row inside the band, its first row, the inbound column above it, no column port" % row0)
+        part = Partition(row0, j0, m, j1)
+        m_all, m = m, m - row0           # from here on m counts the rows of the partition; the engine's rows are relative to row0
         seg = self.segment_rows
         nseg = (m + seg - 1) // seg
         # local alignments prune against the chain's running best score; global ones (NEEDLEMAN_WUNSCH with nothing tracked:
@@ -320,8 +357,13 @@ class BandRunner:
             # by the extents of the whole matrix, not of its own band
             kw.update(prune_blocks=True, prune_rows=m, prune_cols=(n_total if n_total is not None else j1) - j0,
                       share_best=self.world > 1)
+        if row0:
+            # the rest of the band: DP row row0 as it was saved is the first row, its leading cell the boundary column's
+            kw.update(first_row_init_type=INIT_WITH_CUSTOM_DATA, first_row=np.ascontiguousarray(first_row, dtype=np.int32))
         if first:
             kw.update(first_column_init_type=first_col_init_type)
+            if row0:
+                kw.update(first_column_start_offset=row0)
         else:
             # corner cell = first-row cell at column j0-1+1 ... (H of DP cell (0, j0)): zero-initialised
             # rows give (0,-INF); custom rows are handled by the caller feeding row 0 of the stream.
@@ -329,9 +371,16 @@ class BandRunner:
             if first_row_init_type != INIT_WITH_ZEROES:
                 open_ = 3 if first_row_init_type == 1 else 0
                 corner[0, 0] = -2 * j0 - open_ if j0 > 0 else 0
+            if row0:
+                prefix = np.asarray(inbound_prefix, dtype=np.int32).reshape(-1, 2)
+                if len(prefix) != row0 + 1:
+                    raise ValueError("run(row0=%d): inbound_prefix holds %d cells, not %d" % (row0, len(prefix), row0 + 1))
+                if self.inbound_column is not None:
+                    self.inbound_column[:row0 + 1] = prefix
+                corner = prefix[row0:row0 + 1].copy()
             kw.update(first_column_init_type=INIT_WITH_CUSTOM_DATA, first_column=corner,
                       stream_first_column=not p2p, first_column_port=p2p)
-            if self.inbound_column is not None:
+            if self.inbound_column is not None and not row0:
                 self.inbound_column[0] = corner[0]
         if p2p:
             self._exchange_ports(m)
@@ -358,16 +407,19 @@ class BandRunner:
                 raise RuntimeError("band %d/%d: a band to the left failed to start its kernel" % (self.rank, self.world))
             bound = None if int(go[1]) == NO_BOUND else int(go[1])
         try:
-            if first and prune and self.seed_bound and self.world > 1 and n_total is not None:
+            if first and initial_bound is not None:
+                bound = int(initial_bound)
+            elif first and prune and self.seed_bound and self.world > 1 and n_total is not None:
                 if prune_end:
-                    bound = edge_seed_bound(eng, m, n_total, first_row_init_type, first_col_init_type)
+                    bound = edge_seed_bound(eng, m_all, n_total, first_row_init_type, first_col_init_type)
                 else:
-                    bound = chain_seed_bound(eng, m, n_total, recurrence, first_row_init_type, first_col_init_type)
+                    bound = chain_seed_bound(eng, m_all, n_total, recurrence, first_row_init_type, first_col_init_type)
             if prune and bound is not None:
                 kw.update(initial_bound=bound)
             self.initial_bound = bound
             arm()
             eng.streamBegin(part, **kw)
+            self._stream_open = True
         except BaseException:
             if not last and dist is not None:
                 dist.send(token(False, None), dst=self.rank + 1)
@@ -388,15 +440,18 @@ class BandRunner:
                     ln = min(seg, m - r0)
                     buf = self._tensor(ln)
                     dist.recv(buf, src=self.rank - 1)
+                    if self._rx_stop.is_set():         # the run has ended (run's clean-up): nothing more goes to the engine
+                        return
                     if digest_inbound:
                         self.inbound_crc = zlib.crc32(buf.numpy().tobytes(), self.inbound_crc)
+                    a0 = row0 + r0                     # the segment's first row in the whole band
                     if self.inbound_column is not None:
-                        self.inbound_column[r0 + 1:r0 + ln + 1] = buf.numpy()
+                        self.inbound_column[a0 + 1:a0 + ln + 1] = buf.numpy()
                     if inbound_h is not None:          # H of the boundary column at every possible special row
-                        q0 = r0 // 256 + 1
-                        q1 = (r0 + ln) // 256
+                        q0 = a0 // 256 + 1
+                        q1 = (a0 + ln) // 256
                         if q1 >= q0:
-                            inbound_h[q0:q1 + 1] = buf.numpy()[q0 * 256 - 1 - r0:q1 * 256 - r0:256, 0]
+                            inbound_h[q0:q1 + 1] = buf.numpy()[q0 * 256 - 1 - a0:q1 * 256 - a0:256, 0]
                     with lock:
                         eng.streamFeedColumn(r0, buf.numpy())
                         fed[0] = r0 + ln
@@ -428,7 +483,7 @@ class BandRunner:
         # (special rows sit on multiples of the strip height, every strip height is a multiple of 256: the boundary
         #  column's H at every 256th row covers whatever geometry a restart on the int32 kernels picks)
         special_dp, special_next = [], [0]
-        inbound_h = np.zeros(m // 256 + 2, dtype=np.int32) if (special_row_interval > 0 and not first and not p2p) else None
+        inbound_h = np.zeros(m_all // 256 + 2, dtype=np.int32) if (special_row_interval > 0 and not first and not p2p) else None
         if special_row_interval > 0:
             while True:
                 try:
@@ -451,7 +506,7 @@ class BandRunner:
                 except (AlignerError, IndexError):
                     break
                 special_dp.append(int(dp))
-            special_next[0] = sum(1 for dp in special_dp if dp <= done_to)
+            special_next[0] = sum(1 for dp in special_dp if row0 + dp <= done_to)
 
         def flush_special(rows_ok):
             """hands over every special row whose strip is complete; called with the lock held"""
@@ -460,21 +515,23 @@ class BandRunner:
                 if not first and not p2p and fed[0] < dp:
                     return                                  # its boundary cell is still on the way
                 _, cells = eng.streamReadSpecialRow(k)
+                dpa = row0 + dp                             # the row in the whole band
                 if first:
                     c0 = np.array([0 if first_col_init_type == INIT_WITH_ZEROES
-                                   else -2 * dp - (3 if first_col_init_type == 1 else 0), -INF], dtype=np.int32)
+                                   else -2 * dpa - (3 if first_col_init_type == 1 else 0), -INF], dtype=np.int32)
                 elif p2p:
                     c0 = np.array([int(eng.portRead(dp - 1, 1)[0, 0]), -INF], dtype=np.int32)
                 else:
-                    c0 = np.array([int(inbound_h[dp // 256]), -INF], dtype=np.int32)
+                    c0 = np.array([int(inbound_h[dpa // 256]), -INF], dtype=np.int32)
                 if special_row_sink is not None:
-                    special_row_sink(dp, c0, cells)
-                self.special_rows.append(dp)
+                    special_row_sink(dpa, c0, cells)
+                self.special_rows.append(dpa)
                 special_next[0] += 1
 
         # host transport: the chain's running best travels between the rank processes (p2p: between the kernels)
         self.hints = 0
         bx_stop, bx = threading.Event(), None
+        self._bx_stop = bx_stop          # (run's clean-up sets it too)
         if prune and self.world > 1 and not p2p and self._best_group is not None:
             def best_exchange():
                 import torch
@@ -502,7 +559,7 @@ class BandRunner:
 
         rx = None
         if not first and not p2p:
-            rx = threading.Thread(target=receiver, daemon=True)
+            rx = self._rx = threading.Thread(target=receiver, daemon=True)
             rx.start()
         send_q = 0
         # a chain that stands still says where: one line per 10 s without progress on this band (rows completed,
@@ -534,6 +591,7 @@ class BandRunner:
                         eng.streamEnd()
                     except AlignerError:
                         pass
+                    self._stream_open = False
                 if bx is not None:           # (it leaves its loop at the next all_reduce in which every band has said stop)
                     bx.join(timeout=5.0)
                 raise errors[0]
@@ -605,6 +663,7 @@ class BandRunner:
             if before_end is not None:
                 before_end(eng)
             best, _ = eng.streamEnd()
+        self._stream_open = False
         if bx is not None:
             bx.join()
         if errors:
@@ -747,7 +806,7 @@ class InProcessChain:
 
 
 def _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_row_init_type, first_col_init_type, origin, run_kw,
-               extent=None):
+               extent=None, resume=None):
     """one band's stage 1 into the Special Rows Area of `bwork` (band_stage1 and serial_band_stage1 share it): the partition
     directory, the special rows with their boundary cell, the last row, the markers and the tee'd boundary column.  Returns
     (the band's own best as the engine reports it -- for a global run that ends in the last cell, prune_end 0 and nothing
@@ -763,12 +822,18 @@ def _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_r
     area = sra_mod.SpecialRowsArea(sra_mod.special_rows_path(bwork, 1, 0), disk_limit=max(sra_limit, 1))
     part = area.create_partition(oi, oj + j0, oi + m, oj + j1)
     part.set_border_markers(first_row_init_type, j0, first_col_init_type if first else INIT_WITH_CUSTOM_DATA, 0)
+    run_kw = dict(run_kw)
+    kept = []
+    if resume is not None:           # serial_band_stage1(resume=True): where the band starts, what stays of an earlier run
+        kept, restart = resume.begin(part, interval)
+        run_kw.update(restart)
 
     def sink(dp, c0, cells):
         part.write(oi + dp, np.concatenate([np.asarray(c0, dtype=np.int32).reshape(1, 2), cells]))
+        if resume is not None:
+            resume.special_row(dp)
 
     got = {}
-    run_kw = dict(run_kw)
     prev_end = run_kw.pop("before_end", None)
 
     def before_end(eng):
@@ -790,7 +855,7 @@ def _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_r
     if recurrence == NEEDLEMAN_WUNSCH and not run_kw.get("prune_end") and not run_kw.get("track_best", True):
         # both ends in the corners: the result is the last cell of the last band, read from the row just written
         band_best = (m - 1, j1 - 1, int(got["row"][-1, 0])) if last else (-1, -1, -INF)
-    return band_best, part, list(runner.special_rows) + ([m] if m not in runner.special_rows else [])
+    return band_best, part, kept + list(runner.special_rows) + ([m] if m not in runner.special_rows else [])
 
 
 def _write_chain_best(bwork, best, origin=(0, 0)):
@@ -823,7 +888,9 @@ def band_stage1(runner, m, j0, j1, work, sra_limit, n_total=None, recurrence=SMI
     best (include/mi355sw.h, mi355sw_set_prune_end).
     A global run that ends in the last cell (NEEDLEMAN_WUNSCH, track_best=False, prune_end 0): "best" is (m, n, H[m][n]), which
     the last band reads from its last row -- what the traceback through the chain starts from (bands.band_traceback).
-    serial_band_stage1 leaves the same files with the bands run one after the other on one engine."""
+    serial_band_stage1 leaves the same files with the bands run one after the other on one engine.
+    No resume here: serial_band_stage1(resume=True) continues a killed serial chain; a coordinated restart of the ranks of this
+    collective form is a separate piece of work."""
     bwork = os.path.join(work, "FORK.%02d" % runner.rank) if runner.world > 1 else work
     band_best, _part, rows = _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_row_init_type,
                                         first_col_init_type, (0, 0), run_kw)
@@ -840,8 +907,11 @@ class _SerialLink:
     def __init__(self):
         import collections
         self.queue = collections.deque()
+        self.on_segment = None           # on_segment(cells): every row segment of a last column, before it is queued
 
     def send(self, t, dst=None):
+        if self.on_segment is not None and t.dim() == 2:     # (the start token is one row of two int64)
+            self.on_segment(t.numpy())
         self.queue.append(t.clone())
 
     def recv(self, t, src=None):
@@ -852,10 +922,210 @@ class _SerialLink:
         if bound is not None and self.queue:
             self.queue[0][1] = max(int(self.queue[0][1]), int(bound))
 
+    def feed(self, column, row0, segment_rows, bound=None):
+        """what a band that ran in an earlier process would have sent: its start token (with `bound`) and rows row0.. of its last
+        column (`column`: corner cell first) in segments, for the band that is resumed"""
+        import torch
+        self.queue.clear()
+        self.queue.append(torch.tensor([1, NO_BOUND if bound is None else int(bound)], dtype=torch.int64))
+        rows = len(column) - 1
+        for r in range(row0, rows, segment_rows):
+            self.queue.append(torch.from_numpy(np.ascontiguousarray(column[1 + r:1 + min(r + segment_rows, rows)])))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# resume of a serial chain (serial_band_stage1(resume=True)): two files per band next to what band_stage1 leaves
+#   chain.mi355        JSON, written as .tmp and renamed, always AFTER the files it speaks of: the key of the run, the band, and
+#                      either the finished band's record or how far an unfinished band is known to be on disk
+#   last_column.mi355  the band's outbound boundary column, the next band's corner cell first, raw (H, E) int32 pairs, appended
+#                      segment by segment; removed once the next band is done (its C00000000.INIT_WITH_CUSTOM_DATA holds the cells)
+# ---------------------------------------------------------------------------------------------------------------------------
+CHAIN_STATE, CHAIN_COLUMN, CHAIN_STATE_VERSION = "chain.mi355", "last_column.mi355", 1
+
+
+def _save_chain_state(bwork, state):
+    import json
+    fn = os.path.join(bwork, CHAIN_STATE)
+    with open(fn + ".tmp", "w") as f:
+        json.dump(state, f, sort_keys=True)
+        f.write("\n")
+        f.flush()
+        os.fsync(f.fileno())
+    os.replace(fn + ".tmp", fn)
+
+
+def _rows_on_disk(bwork):
+    """DP rows (ids) of the complete special rows under a band's work directory, without creating anything"""
+    rows = []
+    for d, _dirs, files in os.walk(os.path.join(bwork, "special_rows", "stage.01.00")):
+        rows += [int(f, 16) for f in files if len(f) == 8 and all(c in "0123456789ABCDEF" for c in f)]
+    return sorted(rows)
+
+
+def _load_chain_state(bwork, key, band):
+    """the state a band left, checked against this call: None when the band's directory holds nothing to continue"""
+    import json
+    fn = os.path.join(bwork, CHAIN_STATE)
+    if not os.path.exists(fn):
+        if _rows_on_disk(bwork):
+            raise RuntimeError("serial_band_stage1: %s holds special rows but no %s: cannot resume (clean the work directory)"
+                               % (bwork, CHAIN_STATE))
+        return None
+    state = json.load(open(fn))
+    if state.get("version") != CHAIN_STATE_VERSION:
+        raise ValueError("serial_band_stage1: %s is of format version %r, this is version %d (clean the work directory)"
+                         % (fn, state.get("version"), CHAIN_STATE_VERSION))
+    theirs = dict(state.get("key", {}), band=state.get("band"))
+    for name, mine in sorted(dict(key, band=band).items()):
+        if theirs.get(name) != mine:
+            raise ValueError("serial_band_stage1: %s was left by a run with %s = %r, this one has %r (clean the work directory)"
+                             % (fn, name, theirs.get(name), mine))
+    return state
+
+
+def _inbound_file(works, k, m):
+    """where band k's inbound boundary column lies whole ((m + 1) cells, corner first): the last_column.mi355 of the band on
+    its left, or -- band k was done once and that file went -- band k's own tee of it; None when neither is there"""
+    fn = os.path.join(works[k - 1], CHAIN_COLUMN)
+    if os.path.exists(fn) and os.path.getsize(fn) >= 8 * (m + 1):
+        return fn
+    for d, _dirs, files in os.walk(os.path.join(works[k], "special_rows", "stage.01.00")):
+        fn = os.path.join(d, "C00000000.INIT_WITH_CUSTOM_DATA")
+        if "C00000000.INIT_WITH_CUSTOM_DATA" in files and os.path.getsize(fn) == 8 * (m + 1):
+            return fn
+    return None
+
+
+def _corner_cell(first_row_init_type, j):
+    """(H, E) of DP cell (0, j) on the first row: the corner of the band that starts at column j (BandRunner.run)"""
+    h = 0
+    if first_row_init_type != INIT_WITH_ZEROES and j > 0:
+        h = -2 * j - (3 if first_row_init_type == 1 else 0)
+    return np.array([[h, -INF]], dtype=np.int32)
+
+
+def _kernel_prunes(name):
+    """whether the kernel the engine names in its statistics is a pruning instantiation: sw_strip_kernel_pk16<R,track,local,PRUNE..>,
+    sw_strip_kernel<R,local,profile,track,PRUNE> -- the engine may drop a pruning request (include/mi355sw.h), the result is
+    the same.  An engine that names no kernel is taken at its word."""
+    if not name or "<" not in name:
+        return True
+    args = name[name.index("<") + 1:].rstrip(">").split(",")
+    if "pk16_mixed" in name:
+        return len(args) > 2 and args[2] == "true"
+    if "pk16" in name:
+        return len(args) > 3 and args[3] == "true"
+    return len(args) > 4 and args[4] == "true"
+
+
+class _BandResume:
+    """What serial_band_stage1(resume=True) keeps of ONE band while it runs, and where a band that was interrupted starts."""
+
+    def __init__(self, band, bands, bwork, key, m, prev, midband, inbound, link, segment_rows, corner_next, progress):
+        self.band, self.last, self.bwork, self.key, self.m = band, band == bands - 1, bwork, key, m
+        self.prev, self.midband, self.inbound, self.link, self.segment_rows = prev, midband, inbound, link, segment_rows
+        self.corner_next, self.progress = corner_next, progress
+        self.bound = None                # what the chain's bound stands at when this band begins
+        self.runner = None
+        self.state = None
+        self.column = None               # last_column.mi355, open for appending
+        self.row0 = 0
+        self.state_writes = self.column_writes = 0
+
+    def _save(self):
+        _save_chain_state(self.bwork, self.state)
+        self.state_writes += 1
+
+    def _tell(self, event, row):
+        if self.progress is not None:
+            self.progress(event, self.band, row)
+
+    def begin(self, part, interval):
+        """the row the band starts at and everything run() needs for it; the state says so BEFORE anything below that row goes"""
+        m, prev, r = self.m, self.prev, 0
+        column_fn = os.path.join(self.bwork, CHAIN_COLUMN)
+        if self.midband and interval > 0 and prev is not None and not prev.get("done"):
+            on_disk = set(part.rows)
+            rows = [x for x in sorted(prev.get("rows", [])) if x in on_disk and 0 < x < m]
+            if not self.last:            # ... and no further than the outbound column is known to be on disk
+                have = (os.path.getsize(column_fn) // 8 - 1) if os.path.exists(column_fn) else 0
+                durable = min(int(prev.get("column_rows", 0)), have)
+                rows = [x for x in rows if x <= durable]
+            r = rows[-1] if rows else 0
+        kept = [x for x in sorted(part.rows) if 0 < x <= r and x in prev.get("rows", [])] if r else []
+        self.row0 = r
+        self.state = {"version": CHAIN_STATE_VERSION, "key": self.key, "band": self.band, "done": False, "rows": list(kept),
+                      "column_rows": r, "initial_bound": prev.get("initial_bound") if (r and prev) else None, "from_row": r}
+        self._save()
+        for rid in list(part.rows):      # rows below r are written again
+            if rid not in kept:
+                os.remove(os.path.join(part.path, "%08X" % rid))
+        part.rows = list(kept)
+        part.reload()
+        if not self.last:
+            if r:
+                self.column = open(column_fn, "r+b")
+                self.column.truncate(8 * (1 + r))
+                self.column.seek(0, 2)
+            else:
+                self.column = open(column_fn, "wb")
+                self.column.write(self.corner_next.tobytes())
+            self.column.flush()
+            self.link.on_segment = self.segment
+        restart = {}
+        if r:
+            restart = dict(row0=r, first_row=part.read_row(part.i0 + r))
+            if self.inbound is not None:
+                restart["inbound_prefix"] = self.inbound[:r + 1]
+            elif self.state["initial_bound"] is not None:
+                restart["initial_bound"] = self.state["initial_bound"]
+        if self.inbound is not None:     # the band on the left ran in an earlier process: its column comes from its file
+            self.link.feed(self.inbound, r, self.segment_rows, self.bound)
+        return kept, restart
+
+    def _bound_seen(self):
+        if self.runner is not None and self.state["initial_bound"] is None and self.runner.initial_bound is not None:
+            self.state["initial_bound"] = int(self.runner.initial_bound)
+
+    def special_row(self, dp):
+        from . import sra as sra_mod
+        sra_mod.drain()                  # the row's file is in place (written, renamed) before the state names it
+        self._bound_seen()
+        self.state["rows"].append(int(dp))
+        self._save()
+        self._tell("special_row", int(dp))
+
+    def segment(self, cells):
+        self.column.write(np.ascontiguousarray(cells, dtype=np.int32).tobytes())
+        self.column.flush()
+        os.fsync(self.column.fileno())
+        self.column_writes += 1
+        self._bound_seen()
+        self.state["column_rows"] += len(cells)
+        self._save()
+        self._tell("column", self.state["column_rows"])
+
+    def close(self):
+        self.link_off()
+        if self.column is not None:
+            self.column.close()
+            self.column = None
+
+    def link_off(self):
+        if self.link is not None:
+            self.link.on_segment = None
+
+    def finish(self, record):
+        from . import sra as sra_mod
+        sra_mod.drain()
+        self.close()
+        self.state = dict({"version": CHAIN_STATE_VERSION, "key": self.key, "band": self.band, "done": True}, **record)
+        self._save()
+
 
 def serial_band_stage1(engine, m, limits, work, sra_limit, n_total=None, recurrence=SMITH_WATERMAN,
                        first_row_init_type=INIT_WITH_ZEROES, first_col_init_type=INIT_WITH_ZEROES, prune_blocks=False,
-                       seed_bound=True, segment_rows=1 << 16, origin=(0, 0), extent=None, **run_kw):
+                       seed_bound=True, segment_rows=1 << 16, origin=(0, 0), extent=None, resume=False, progress=None, **run_kw):
     """The chain of band_stage1, band after band on ONE engine by one process -- the reference's `--split=N --part=1..N`
     sequence: band k runs to its end, its last column (streamReadColumn, on the host) becomes band k+1's first column
     (streamFeedColumn).  limits = band_limits(n, weights): band k = columns [limits[k], limits[k+1]).  Every `work`/FORK.NN
@@ -868,43 +1138,144 @@ def serial_band_stage1(engine, m, limits, work, sra_limit, n_total=None, recurre
     are absolute, `limits` and `m` relative to it; extent = (rows, columns) of the untrimmed matrix, which the spacing of the
     special rows follows (default: m x n_total).
     Returns {"best": the chain's best (i, j, score) in 1-based DP coordinates, "bands": [per band {"best" (its own, 0-based
-    cell), "work", "special_rows", "seconds", "pruned_cells", "initial_bound"}], "limits"}."""
+    cell), "work", "special_rows", "seconds", "pruned_cells", "initial_bound"}], "limits"}.
+
+    resume=True: a chain that was killed continues from what it left on disk, and a chain that runs through leaves the same
+    tree plus one `chain.mi355` per band (the state: the key of the run, the band, `done` and the band's record, or for an
+    unfinished band the special rows and the rows of its outbound column known to be on disk; written as .tmp and renamed,
+    always after the files it speaks of).  While band k runs, `last_column.mi355` in its directory takes its outbound column
+    segment by segment (the next band's corner cell first, raw (H, E) pairs); it goes once band k+1 is done, whose
+    C00000000.INIT_WITH_CUSTOM_DATA then holds the same cells.  On entry leftover *.tmp files are removed; bands whose state
+    says done and whose last row is on disk are skipped, their candidates, bounds and statistics taken from the state, so that
+    the next band starts from the bound the uninterrupted chain would have used; the first band that is not done reads its
+    inbound column from the file of the band on its left.  A chain that tracks nothing (track_best=False: the global and the
+    edge forms) restarts that band at row r, the largest special row complete on disk that the durable part of its outbound
+    column has reached (the last band: the largest complete one; none: row 0) -- BandRunner.run(row0=r); rows [0, r] of every
+    file stay, what lies below is written again.  A chain that TRACKS A BEST CELL (a local one) restarts the band at row 0:
+    the stream hands out exact best cells at streamEnd only, a best seen in the rows above r could not be located -- the gap
+    that remains.  So does the last band of a chain that may end on the last column (its edge cells above r would be lost).
+    If the engine drops the pruning request of a partition that starts at r, the rest runs unpruned, the band's record says
+    "pruned_after_resume": False and the result is the same.
+    Refused before anything runs: a state whose key differs from this call's (ValueError naming the field), a state of
+    another format version (ValueError), a band directory with special rows and no state (RuntimeError).  An empty work
+    directory is a fresh run.  The return value gains "resumed": {"bands_skipped", "band", "from_row"} (None for a fresh
+    run), "already_done" (every band was done: no stream is begun), and per band "skipped", "state_writes", "column_writes".
+    progress(event, band, row): called at "band_begin", at "special_row" once the row and the state naming it are on disk, at
+    "column" once a segment of the outbound column and the state counting it are, and at "band_end"; an exception out of it
+    (or out of a sink) ends the run with the stream closed -- what a test interrupts a chain with.
+    band_stage1 over ranks has no resume: a coordinated restart of several processes is another piece of work."""
     N = len(limits) - 1
     if N < 1 or any(limits[k] >= limits[k + 1] for k in range(N)) or limits[0] != 0:
         raise ValueError("serial_band_stage1: limits %r are no chain of bands" % (list(limits),))
     n_total = limits[-1] if n_total is None else n_total
     link = _SerialLink() if N > 1 else None
     prune_end = run_kw.get("prune_end", 0)
+    works = [os.path.join(work, "FORK.%02d" % k) if N > 1 else work for k in range(N)]
+    # ---- resume: what the bands left, checked before anything runs ----
+    key, states, k_first = None, [None] * N, 0
+    if resume:
+        from . import sra as sra_mod
+        em, en = extent if extent is not None else (m, n_total)
+        key = {"m": int(m), "limits": [int(x) for x in limits], "origin": [int(x) for x in origin],
+               "extent": [int(x) for x in extent] if extent is not None else None, "n_total": int(n_total),
+               "recurrence": int(recurrence), "first_row_init_type": int(first_row_init_type),
+               "first_col_init_type": int(first_col_init_type), "track_best": bool(run_kw.get("track_best", True)),
+               "prune_end": int(prune_end), "prune_blocks": bool(prune_blocks), "sra_limit": int(sra_limit),
+               "special_row_interval": int(sra_mod.flush_interval(em, en, sra_limit)) if sra_limit > 0 else 0}
+        states = [_load_chain_state(works[k], key, k) for k in range(N)]
+        for bwork in works:                               # leftovers of a killed run
+            for d, _dirs, files in os.walk(bwork):
+                for f in files:
+                    if f.endswith(".tmp"):
+                        os.remove(os.path.join(d, f))
+        # bands that are done -- the state says so and the completion marker, the last row, is on disk -- are not run again;
+        # the first band that is not needs the column of the band on its left, whole
+        while k_first < N and states[k_first] is not None and states[k_first].get("done") and m in _rows_on_disk(works[k_first]):
+            k_first += 1
+        while 0 < k_first < N:
+            if _inbound_file(works, k_first, m) is not None:
+                break
+            k_first -= 1                                  # (no column to start from: the band on the left runs again, from row 0)
+            states[k_first] = dict(states[k_first], done=False, rows=[], column_rows=0)
+    midband = not run_kw.get("track_best", True)          # a chain that tracks a best cell restarts its band at row 0
+    resumed = None
+    if resume and any(s is not None for s in states):
+        resumed = {"bands_skipped": k_first, "band": k_first if k_first < N else None, "from_row": 0}
     bands, cands, bound, first_bound = [], [], None, None
+    from_row_before = 0
     for k in range(N):
-        runner = BandRunner(engine, dist=link, rank=k, world=N, segment_rows=segment_rows, prune_blocks=prune_blocks,
-                            transport="host", seed_bound=seed_bound)
-        if k > 0:
-            link.raise_bound(bound)
-        bwork = os.path.join(work, "FORK.%02d" % k) if N > 1 else work
-        t0 = time.time()
-        band_best, _part, rows = _band_area(runner, m, limits[k], limits[k + 1], bwork, sra_limit, n_total, recurrence,
-                                            first_row_init_type, first_col_init_type, origin, run_kw, extent)
-        mine = runner.edge_best if prune_end else band_best
-        mine = tuple(int(x) for x in mine) if mine is not None else (-1, -1, -INF)
+        bwork = works[k]
+        if resume and k < k_first:                        # done in an earlier run: its record stands in for it
+            st = states[k]
+            mine, own_bound = tuple(int(x) for x in st["best"]), st["initial_bound"]
+            rec = {"best": mine, "work": bwork, "special_rows": list(st["special_rows"]), "seconds": st["seconds"],
+                   "pruned_cells": int(st["pruned_cells"]), "initial_bound": own_bound, "restarts": int(st["restarts"]),
+                   "skipped": True}
+        else:
+            runner = BandRunner(engine, dist=link, rank=k, world=N, segment_rows=segment_rows, prune_blocks=prune_blocks,
+                                transport="host", seed_bound=seed_bound)
+            keeper = None
+            if resume:
+                inbound = None
+                # (the band on the left ran in an earlier process, or in this one from a row below 0: its column is its file)
+                if k > 0 and (k == k_first or from_row_before):
+                    inbound = np.fromfile(_inbound_file(works, k, m), dtype=np.int32, count=2 * (m + 1)).reshape(-1, 2)
+                # (the last band of a chain that may end on the last column starts over: its edge cells above the row are gone)
+                keeper = _BandResume(k, N, bwork, key, m, states[k], midband and k == k_first and not (k == N - 1 and prune_end & 2),
+                                     inbound, link, segment_rows, _corner_cell(first_row_init_type, limits[k + 1]), progress)
+                keeper.runner, keeper.bound = runner, bound
+                os.makedirs(bwork, exist_ok=True)
+                if progress is not None:
+                    progress("band_begin", k, 0)
+            if k > 0 and (keeper is None or keeper.inbound is None):
+                link.raise_bound(bound)
+            t0 = time.time()
+            try:
+                band_best, _part, rows = _band_area(runner, m, limits[k], limits[k + 1], bwork, sra_limit, n_total, recurrence,
+                                                    first_row_init_type, first_col_init_type, origin, run_kw, extent, keeper)
+            finally:
+                if keeper is not None:
+                    keeper.close()
+            mine = runner.edge_best if prune_end else band_best
+            mine = tuple(int(x) for x in mine) if mine is not None else (-1, -1, -INF)
+            own_bound = runner.initial_bound
+            st = engine.getStatistics() if hasattr(engine, "getStatistics") else {}
+            rec = {"best": mine, "work": bwork, "special_rows": rows, "seconds": time.time() - t0,
+                   "pruned_cells": int(st.get("pruned_cells", 0)), "initial_bound": own_bound, "restarts": runner.restarts}
+            if keeper is not None:
+                rec.update(skipped=False, state_writes=keeper.state_writes + 1, column_writes=keeper.column_writes)
+                from_row_before = keeper.row0
+                if keeper.row0:
+                    resumed["from_row"] = keeper.row0
+                    if runner.prune_blocks and not run_kw.get("track_best", True):
+                        rec["pruned_after_resume"] = _kernel_prunes(st.get("kernel"))
         cands.append(mine)
         if k == 0:
-            first_bound = runner.initial_bound
-        if runner.initial_bound is not None:
-            bound = runner.initial_bound if bound is None else max(bound, runner.initial_bound)
+            first_bound = own_bound
+        if own_bound is not None:
+            bound = own_bound if bound is None else max(bound, own_bound)
         # a score some alignment of the asked form reaches: a local best; a last-row cell of a chain that may end on the last row
         if (recurrence == SMITH_WATERMAN or (prune_end & 1 and k < N - 1)) and mine[2] > -INF:
             bound = mine[2] if bound is None else max(bound, mine[2])
-        st = engine.getStatistics() if hasattr(engine, "getStatistics") else {}
-        bands.append({"best": mine, "work": bwork, "special_rows": rows, "seconds": time.time() - t0,
-                      "pruned_cells": int(st.get("pruned_cells", 0)), "initial_bound": runner.initial_bound,
-                      "restarts": runner.restarts})
+        if resume and not rec["skipped"]:
+            keeper.finish({"best": list(mine), "initial_bound": own_bound, "bound_after": bound, "first_bound": first_bound,
+                           "special_rows": [int(x) for x in rows], "pruned_cells": rec["pruned_cells"],
+                           "restarts": int(rec["restarts"]), "seconds": rec["seconds"]})
+            if k > 0 and os.path.exists(os.path.join(works[k - 1], CHAIN_COLUMN)):
+                os.remove(os.path.join(works[k - 1], CHAIN_COLUMN))      # this band's tee'd first column holds the same cells
+            if progress is not None:
+                progress("band_end", k, m)
+        bands.append(rec)
     best = canonical_best(cands)
     if prune_blocks:
         check_chain_bound(best[2], first_bound)
     for b in bands:
         out = _write_chain_best(b["work"], best, origin)
-    return {"best": tuple(out), "bands": bands, "limits": list(limits)}
+    ret = {"best": tuple(out), "bands": bands, "limits": list(limits)}
+    if resume:
+        ret["resumed"] = resumed
+        ret["already_done"] = k_first >= N
+    return ret
 
 
 def band_traceback(runner, seq0, seq1, work, limits, **kw):

@@ -160,7 +160,7 @@ def chain_form(alignment_start, alignment_end):
 @sra_mod.with_async_files
 def align_bands(aligner, seq0, seq1, work, weights, alignment_start=AT_ANYWHERE, alignment_end=AT_ANYWHERE, sra_limit=0,
                 block_pruning=True, max_partition_size=16, progress=None, max_alignments=1, ram_limit=0, prune_global=False,
-                prune_traceback=False, prune_edges=False):
+                prune_traceback=False, prune_edges=False, resume=False, segment_rows=1 << 16):
     """align() with stage 1 taken in len(weights) column bands, one after the other on `aligner` (bands.serial_band_stage1:
     band k gets weights[k] / sum(weights) of the columns, its own Special Rows Area in `work`/FORK.NN and `sra_limit` of
     budget, like a --split node), and the alignment traced back through the chain (band_traceback.traceback_serial).  So one
@@ -169,7 +169,12 @@ def align_bands(aligner, seq0, seq1, work, weights, alignment_start=AT_ANYWHERE,
     seconds per stage (stage 1 included), and "keeper".
     Block pruning applies where a band's stage 1 prunes: local alignments (block_pruning), global ones (prune_global),
     alignments that end on an edge (prune_edges).  ram_limit is not split over bands: rows are kept on disk.
-    With ONE band this is align() itself: same path, same files."""
+    With ONE band this is align() itself: same path, same files.
+    resume=True: stage 1 continues a chain that was killed from what it left in `work` (bands.serial_band_stage1(resume=True):
+    bands that are done are skipped, the band that was interrupted restarts at its last durable special row where the chain
+    tracks nothing, at row 0 where it tracks a best cell) and leaves one chain.mi355 per band; stages 2 to 6 run as always on
+    what stage 1 left -- running them again costs seconds.  The record then carries "resumed" (serial_band_stage1's).  With one
+    weight it is align(), which resumes by itself.  segment_rows: the rows per segment of the boundary column between two bands."""
     from . import bands as bands_mod
     from . import band_traceback as bt
     from .manager import AT_SEQUENCE_1_AND_2
@@ -202,13 +207,17 @@ def align_bands(aligner, seq0, seq1, work, weights, alignment_start=AT_ANYWHERE,
     t = time.time()
     aligner.setSequences(d0[bi0:bi1], d1[bj0:bj1])
     try:
+        if resume:
+            form = dict(form, resume=True)
         r1 = bands_mod.serial_band_stage1(aligner, bi1 - bi0, rel, work, sra_limit, prune_blocks=prune, origin=(bi0, bj0),
-                                          extent=(len(d0), len(d1)), **form)
+                                          extent=(len(d0), len(d1)), segment_rows=segment_rows, **form)
     finally:
         aligner.unsetSequences()
     secs[1] = time.time() - t
     out = {"best": r1["best"], "alignment": None, "text": None, "crosspoints": {}, "seconds": secs, "stage1": r1, "alignments": [],
            "bands": [{"band": k, "role": "idle", "crosspoints": {}, "seconds": {1: b["seconds"]}} for k, b in enumerate(r1["bands"])]}
+    if resume:
+        out["resumed"] = r1["resumed"]
     if r1["best"][2] <= -INF or r1["best"][0] < 0:
         return out
     limits = [bj0 + x for x in rel]

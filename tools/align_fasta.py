@@ -15,6 +15,10 @@ MI355X) behind the handful of MASA-CUDAlign options that concern the path -- not
       --split=N | --split=W1,W2,...  stage 1 in N column bands of equal width (or of the given weights), one after the other on
                                 the GPU, each with its own Special Rows Area of --disk-size in <work>/FORK.NN, and the alignment
                                 traced back through the chain (pipeline.align_bands; one alignment, no --ram-size)
+      --resume                  with --split: continue a chain that was killed from what it left in the work directory -- bands
+                                that are done are skipped, the band that was interrupted restarts at its last durable special
+                                row (a local chain: at its row 0); leaves one chain.mi355 per FORK.NN.  Without --split a killed
+                                stage 1 resumes by itself
       --wide-alphabet           sequences with 15 to 62 letters in common (all IUPAC codes, ...) run on the packed kernels too
                                 (MI355SW_F_WIDE_ALPHABET; same alignment, off by default)
 
@@ -46,6 +50,7 @@ def main(argv):
     trim, rev, comp, clear_n = [0, 0, 0, 0], [False, False], [False, False], False
     prune_global = prune_traceback = wide_alphabet = prune_edges = False
     weights = None
+    resume = False
     files = []
     for a in argv:
         if a.startswith("--work-dir="):
@@ -81,6 +86,8 @@ def main(argv):
         elif a.startswith("--split="):
             v = [int(x) for x in a[8:].split(",")]
             weights = [1] * v[0] if len(v) == 1 else v
+        elif a == "--resume":
+            resume = True
         elif a.startswith("--gpu="):
             device = int(a[6:])
         elif a == "--stage-1":
@@ -107,9 +114,10 @@ def main(argv):
         elif weights is not None and len(weights) > 1:
             out = pipeline.align_bands(al, seqs[0], seqs[1], work, weights, alignment_start=edge[edges[0]], alignment_end=edge[edges[1]],
                                        sra_limit=limit, block_pruning=prune, max_alignments=count, prune_global=prune_global,
-                                       prune_traceback=prune_traceback, prune_edges=prune_edges)
+                                       prune_traceback=prune_traceback, prune_edges=prune_edges, **({"resume": True} if resume else {}))
             res = {"best": list(out["best"]), "seconds": {str(k): v for k, v in out["seconds"].items()},
                    "crosspoints": {str(k): v for k, v in out["crosspoints"].items()}, "keeper": out.get("keeper"),
+                   **({"resumed": out.get("resumed")} if resume else {}),
                    "bands": [{"band": b["band"], "role": b["role"], "crosspoints": {str(k): v for k, v in b["crosspoints"].items()},
                               "seconds": {str(k): v for k, v in b["seconds"].items()}} for b in out["bands"]],
                    "alignments": [os.path.join(work, "alignment.00.txt")] if out["text"] is not None else []}
