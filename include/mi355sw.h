@@ -148,6 +148,24 @@ typedef struct {
                                                mi355sw_set_sequences; the results are the same bytes with the flag on and off.  Pairs with up to 14
                                                common byte values are not affected.  MI355SW_F_FORCE_GENERIC_COMPARE wins over it; with
                                                MI355SW_F_FORCE_INT32, and for an overflow rerun, the int32 byte-compare kernel runs on the codes */
+#define MI355SW_F_INT32_PRUNE_GLOBAL 131072 /* block pruning of GLOBAL alignments on the int32 kernel family too (additive in ABI 8; off by default: without it
+                                               every run is what it was, an int32 global sweep computes every cell).  With it, a stream that runs on
+                                               the int32 kernels -- 15 or more common byte values (63 or more with MI355SW_F_WIDE_ALPHABET),
+                                               MI355SW_F_FORCE_INT32, the rerun after an MI355SW_EOVERFLOW16 report (mi355sw_align_partition keeps the
+                                               request on that attempt) -- prunes by the packed kernels' last-cell rule when prune_blocks is set, the
+                                               recurrence is not SMITH_WATERMAN and track_best is 0: the goal is the last cell of the super-partition
+                                               (prune_rows / prune_cols), the unit is one 64-step slab of a strip, skipped cells read H = E = F = -INF
+                                               (mi355sw_stats.kernel: sw_strip_kernel<R,false,..,false,true>; pruned_cells + processed_cells = m * n).
+                                               initial_bound starts the bound and MI355SW_EBOUND holds the result against it at mi355sw_stream_end as on
+                                               the packed kernels.  A band of a chain (column ports, share_best) prunes against the distances to the
+                                               end of the super-partition with its own finds and its own initial_bound; the running best of the other
+                                               bands is not relayed to this family (the chain's words are in the packed kernels' domain).
+                                               NOT served, every cell computed as before: the edge rule (mi355sw_set_prune_end), goal bounds
+                                               (mi355sw_set_goal_bounds), reproducible pruning (MI355SW_F_DETERMINISTIC_PRUNE is ignored by this
+                                               family), the partitions of mi355sw_align_partitions, and the diagonal seed -- it needs the packed
+                                               kernels, so a caller hands a bound in through initial_bound (mi355sw_seed_bound makes one where the
+                                               pair runs on the packed kernels).  No pruning window, fast-forward or retire: every strip walks the
+                                               whole width. */
 #define MI355SW_F_NO_HOST_COUNTER 512       /* the kernel does not mirror its strip counter into host memory (measurements) */
 #define MI355SW_V_MESSAGES 1                /* one line per noteworthy event (overflow reruns, the diagonal seed, ...) */
 #define MI355SW_V_JOBS 2                    /* timing of every mi355sw_align_partition job */

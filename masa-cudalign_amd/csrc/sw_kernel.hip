@@ -174,8 +174,48 @@ __device__ __forceinline__ void wave_step(LaneState<R>& st, WaveLds* lds, const 
 // (sw_kernel_pk16.inc, SW_PRUNE_MARGIN included).  Skipped cells read H = 0, E = F = -INF.  No window, no fast-forward: this
 // family takes the pairs the packed kernel cannot (more than 14 common byte values) and its reruns.
 #define SW32_PRUNE_MARGIN 8
+// PRUNE && !SW (global alignments; opt-in, MI355SW_F_INT32_PRUNE_GLOBAL): the packed family's last-cell rule (DESIGN.md
+// section 4, "Global"; AbstractBlockPruning.cpp:92-109) on int32 values, slab by slab.  gbest holds a running LOWER bound of
+// H[m][n] - GAP_FIRST of the super-partition; dI / dJ below are a cell's rows / columns to that cell.
+//   * every computed slab of full rows and columns contributes nw_lower32 of each lane's chunk maximum;
+//   * a slab goes when nw_upper32 of everything that enters it -- each lane's lane_entry, the bus cells above -- is below it
+//     (strict: ties are kept);
+//   * skipped cells read H = E = F = -INF; a lane that holds nothing (t <= NEG_INF / 2) enters nothing;
+//   * what a lane carries over a chunk boundary and every cell stored is clamped at -INF (clamp_void32): next to skipped
+//     cells a computed cell sinks by up to 5 per step, and the clamp bounds that to one slab ("No wrap").
+// The margin is the packed family's NW_PRUNE_MARGIN, not SW32_PRUNE_MARGIN: what enters a slab through its corner -- the bus
+// cell diagonally above its first cell, the bottom cell of the lane above one column back -- is within one step (5) of a
+// value the test does look at, and one cell of position moves this bound by up to 3 where the local bound moves by 1; 16
+// covers 5 + 2 * 3 with room, and with the same margin the two families' skip counts can be held against each other.
+#define NW32_PRUNE_MARGIN 16
+// Upper bound (t domain) of the last cell's score over every path through a cell that holds at most `t` and has between
+// di - si and di rows and between dj - sj and dj columns to go: every diagonal step a match, the gap that the imbalance
+// forces at its extension price (the cell may sit inside an open gap).  The position terms are the most favourable of the span.
+__device__ __forceinline__ int nw_upper32(const int t, const int di, const int dj, const int si, const int sj) {
+    if (t <= NEG_INF / 2) return NEG_INF - 1;             // nothing enters here: below every lower bound, known or not
+    const int dlo = dj - sj - di, dhi = dj - di + si;      // range of (columns left - rows left) over the cells
+    const int dmin = min(max(0, max(dlo, -dhi)), 400000000);   // (int32 headroom; a weaker bound, never a wrong one)
+    return t + min(di, dj) - 2 * dmin + NW32_PRUNE_MARGIN;
+}
+// Lower bound (t domain) of the last cell's score from a cell that holds `t`, a score some path really reaches, wherever it
+// lies among cells with at most `kmax` diagonal steps to go and an imbalance of at most `dmax`: mismatches down the diagonal,
+// then one gap (dec = distMin * -mismatch + gap_open + gaps * gap_ext).  The position terms are the least favourable of the span.
+__device__ __forceinline__ int nw_lower32(const int t, const long long kmax, const long long dmax) {
+    const long long lb = (long long) t - 3 * kmax - 3 - 2 * dmax;
+    return lb > (long long) NEG_INF ? (int) lb : NEG_INF;
+}
+// a lane's state at a chunk boundary, -INF images pulled back up to -INF (t domain: -INF - GAP_FIRST)
+template <int R>
+__device__ __forceinline__ void clamp_void32(LaneState<R>& st) {
+#pragma unroll
+    for (int r = 0; r < R; r++) { st.tl[r] = max(st.tl[r], NEG_INF - GAP_FIRST); st.e[r] = max(st.e[r], NEG_INF); }
+    st.tup_prev = max(st.tup_prev, NEG_INF - GAP_FIRST);
+    st.tbot = max(st.tbot, NEG_INF - GAP_FIRST);
+    st.fbot = max(st.fbot, NEG_INF);
+}
 template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false>
 __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, const int s_in, WaveLds* lds, const int lane) {
+    constexpr bool NWP = PRUNE && !SW;                  // the global (last-cell) rule
     const UniformArgs a = uniform_args(ap);
     const int s = __builtin_amdgcn_readfirstlane(s_in);
     const int n = a->n;
@@ -276,6 +316,16 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
             }
             if (PRUNE) {
                 gseen = max(gseen, poll_agent(a->gbest_in));
+                if (NWP) {
+                    if (!ragged && col0 >= 2 * CHUNK && col0 + CHUNK <= n) {
+                        // what enters the slab: the lane's own last column (its R rows, column col0 - lane - 1, one column
+                        // of room on either side) and the bus cell of its column (the row above the strip; its left
+                        // neighbour is the slab's corner)
+                        const int own = nw_upper32(lane_entry, pr_rows - lane * R, pr_cols - col0 + lane + 2, R - 1, 2);
+                        const int top = nw_upper32(hf.x - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, 1);
+                        skip = !__any(max(own, top) >= gseen);
+                    }
+                } else
                 if (!ragged && col0 >= 2 * CHUNK && col0 + CHUNK <= n) {
                     // (lane k is k columns behind lane 0: the slab touches columns col0 - 63 .. col0 + 63)
                     const int left = min(pr_rows + 2, pr_cols + 1 - (col0 - CHUNK));
@@ -301,11 +351,13 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
         int cm = NEG_INF;
         if (PRUNE && skip) {
             // the slab is not computed: every cell in it counts as H = 0 (t = -5), E = F = -INF
+            // (global rule: H = -INF as well, and the lane then holds nothing -- cm stays at -INF)
+            const int t_skip = NWP ? NEG_INF - GAP_FIRST : -GAP_FIRST;
 #pragma unroll
-            for (int r = 0; r < R; r++) { st.tl[r] = -GAP_FIRST; st.e[r] = NEG_INF; }
-            st.tup_prev = -GAP_FIRST; st.tbot = -GAP_FIRST; st.fbot = NEG_INF;
-            lds->out_tf[lane] = make_int2(-GAP_FIRST, NEG_INF);
-            cm = -GAP_FIRST;
+            for (int r = 0; r < R; r++) { st.tl[r] = t_skip; st.e[r] = NEG_INF; }
+            st.tup_prev = t_skip; st.tbot = t_skip; st.fbot = NEG_INF;
+            lds->out_tf[lane] = make_int2(t_skip, NEG_INF);
+            if (!NWP) cm = -GAP_FIRST;
             pruned_slabs++;
         } else if (ragged) {
 #pragma unroll 2
@@ -320,7 +372,29 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
             for (int u = 0; u < CHUNK; u++)
                 wave_step<R, SW, PROFILE, false, TRACK, false, PRUNE>(st, lds, u, lane, jl, n, nvalid, 63, R - 1, feed, c1, &cm);
         }
-        if (PRUNE) {
+        if (NWP) {
+            // what the lane can hand on, as below; after a skipped slab it holds nothing
+            lane_entry = skip ? NEG_INF : max(cm, masked ? lane_entry : NEG_INF);
+            if (!skip) {
+                clamp_void32<R>(st);
+                // what this slab's cells say about H[m][n] from below.  The lane's maximum is the score of one of its cells --
+                // its R rows, columns col0 - lane .. + 63 -- wherever it is: only slabs of full rows and columns are asked
+                int lbv = NEG_INF;
+                if (!masked && !ragged) {
+                    const long long ki = (long long) pr_rows - lane * R, dj = (long long) pr_cols - col0 + lane;
+                    const long long dhi = dj - (ki - (R - 1)), dlo = (dj - 63) - ki;
+                    lbv = nw_lower32(cm, ki < dj ? ki : dj, dhi > -dlo ? dhi : -dlo);
+                }
+                if (__any(lbv > gseen)) {
+                    int w = lbv;
+#pragma unroll
+                    for (int d = 32; d >= 1; d >>= 1) w = max(w, __shfl_xor(w, d));
+                    w = __builtin_amdgcn_readfirstlane(w);
+                    if (lane == 0) atomicMax(a->gbest, w);
+                    gseen = max(gseen, w);
+                }
+            }
+        } else if (PRUNE) {
             // what the lane can hand on (a chunk it sat out entirely -- masked steps -- keeps what it held), and what the others learn
             lane_entry = max(cm, skip ? -GAP_FIRST : (masked ? lane_entry : NEG_INF));
             if (!skip && __any(cm > gseen)) {
@@ -341,7 +415,8 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
             const int2 tf = lds->out_tf[lane];
             const int col = col0 - emit_lane + lane;
             if (col >= 0 && col < n) {
-                const int2 hf = make_int2(tf.x + GAP_FIRST, tf.y);
+                int2 hf = make_int2(tf.x + GAP_FIRST, tf.y);
+                if (NWP) hf = make_int2(max(hf.x, NEG_INF), max(hf.y, NEG_INF));   // (-INF images stay at -INF: see clamp_void32)
                 st_agent2(&a->bus[col], hf);
                 if (special != nullptr) special[col] = hf;
                 if (lastrow != nullptr) lastrow[col] = hf;
@@ -465,6 +540,9 @@ static hipError_t launch_r(const KernelArgs* a, int grid, hipStream_t stream, bo
     if (sw && prune) {        // block pruning: local alignments with their best score tracked
         if (profile) hipLaunchKernelGGL((sw_strip_kernel<R, true, true, true, true>), dim3(grid), dim3(64), 0, stream, a);
         else hipLaunchKernelGGL((sw_strip_kernel<R, true, false, true, true>), dim3(grid), dim3(64), 0, stream, a);
+    } else if (prune) {       // ... and global ones whose goal is the last cell, nothing tracked (MI355SW_F_INT32_PRUNE_GLOBAL)
+        if (profile) hipLaunchKernelGGL((sw_strip_kernel<R, false, true, false, true>), dim3(grid), dim3(64), 0, stream, a);
+        else hipLaunchKernelGGL((sw_strip_kernel<R, false, false, false, true>), dim3(grid), dim3(64), 0, stream, a);
     } else if (sw) {
         if (profile) { if (track) LAUNCH(true, true, true); else LAUNCH(true, true, false); }
         else         { if (track) LAUNCH(true, false, true); else LAUNCH(true, false, false); }
@@ -482,7 +560,8 @@ hipError_t launch_strip_kernel(const KernelArgs& a, KernelArgs* dargs, int rows_
     if (e != hipSuccess) return e;
     e = hipStreamSynchronize(stream);      // `a` is a host temporary
     if (e != hipSuccess) return e;
-    const bool prune = a.prune != 0 && sw && track;
+    // (the runtime sets a.prune for this family where an instantiation exists: local and tracked, or global and not tracked)
+    const bool prune = a.prune != 0 && (sw ? track : !track);
     switch (rows_per_lane) {
     case 4: return launch_r<4>(dargs, grid, stream, sw, profile, track, prune);
     case 8: return launch_r<8>(dargs, grid, stream, sw, profile, track, prune);

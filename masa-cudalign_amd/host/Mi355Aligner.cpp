@@ -106,6 +106,7 @@ void Mi355Aligner::initialize() {
     if (params->getStripRows() > 0) config.rows_per_lane = params->getStripRows() / 64;
     if (params->getNoDiagonalSeed()) config.flags |= MI355SW_F_NO_DIAGONAL_SEED;
     if (params->getWideAlphabet()) config.flags |= MI355SW_F_WIDE_ALPHABET;
+    if (params->getInt32PruneGlobal()) config.flags |= MI355SW_F_INT32_PRUNE_GLOBAL;
     config.flags |= params->getEngineFlags();
     config.verbosity = params->getEngineVerbosity();
     if (params->getBlockColumns() > 0) {

@@ -29,6 +29,9 @@
                            MASA-Core's stage 1 only asks for pruning when the alignment may end\n\
                            anywhere; with this option the engine also prunes whenever the score is\n\
                            read from the last cell, against a lower bound of that cell.\n\
+--int32-prune-global    With --prune-global: sequences that run on the int32 kernels (15 or more letters in\n\
+                           common without --wide-alphabet, 63 or more with it, reruns after a 16-bit overflow)\n\
+                           prune a global alignment too, slab by slab.  Same results; off by default.\n\
 --no-diagonal-seed      Pruning runs of large matrices (8 Mi x 8 Mi and more) first sweep a narrow band\n\
                            along the diagonal and start their pruning bound from the score found there;\n\
                            this option leaves that pass out (use it with --max-alignments > 1: a strong\n\
@@ -54,6 +57,7 @@
 #define ARG_ENGINE_FLAGS 0x1008
 #define ARG_ENGINE_VERBOSITY 0x1009
 #define ARG_WIDE_ALPHABET 0x100a
+#define ARG_INT32_PRUNE_GLOBAL 0x100b
 
 static struct option long_options[] = {
     {"gpu",        required_argument, 0, ARG_GPU},
@@ -62,6 +66,7 @@ static struct option long_options[] = {
     {"strip-rows", required_argument, 0, ARG_STRIP_ROWS},
     {"block-columns", required_argument, 0, ARG_BLOCK_COLUMNS},
     {"prune-global", no_argument, 0, ARG_PRUNE_GLOBAL},
+    {"int32-prune-global", no_argument, 0, ARG_INT32_PRUNE_GLOBAL},
     {"no-diagonal-seed", no_argument, 0, ARG_NO_DIAGONAL_SEED},
     {"wide-alphabet", no_argument, 0, ARG_WIDE_ALPHABET},
     {"engine-flags", required_argument, 0, ARG_ENGINE_FLAGS},
@@ -70,7 +75,7 @@ static struct option long_options[] = {
 };
 
 Mi355AlignerParameters::Mi355AlignerParameters() : gpu(MI355_DETECT_FASTEST_GPU), waves(0), stripRows(0), blockColumns(0), pruneGlobal(0), noDiagonalSeed(0),
-    wideAlphabet(0), engineFlags(0), engineVerbosity(0) {}
+    wideAlphabet(0), int32PruneGlobal(0), engineFlags(0), engineVerbosity(0) {}
 Mi355AlignerParameters::~Mi355AlignerParameters() {}
 
 void Mi355AlignerParameters::printUsage() const {
@@ -179,6 +184,9 @@ int Mi355AlignerParameters::processArgument(int argc, char** argv) {
         break;
     case ARG_PRUNE_GLOBAL:
         pruneGlobal = 1;
+        break;
+    case ARG_INT32_PRUNE_GLOBAL:
+        int32PruneGlobal = 1;
         break;
     case ARG_NO_DIAGONAL_SEED:
         noDiagonalSeed = 1;

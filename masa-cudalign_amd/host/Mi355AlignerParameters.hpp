@@ -25,6 +25,7 @@ public:
     int getPruneGlobal() const { return pruneGlobal; }     /* --prune-global: block pruning of partitions whose goal is the last cell */
     int getNoDiagonalSeed() const { return noDiagonalSeed; }   /* --no-diagonal-seed: MI355SW_F_NO_DIAGONAL_SEED */
     int getWideAlphabet() const { return wideAlphabet; }       /* --wide-alphabet: MI355SW_F_WIDE_ALPHABET */
+    int getInt32PruneGlobal() const { return int32PruneGlobal; }   /* --int32-prune-global: MI355SW_F_INT32_PRUNE_GLOBAL */
     int getEngineFlags() const { return engineFlags; }         /* --engine-flags=N: MI355SW_F_* bits OR-ed into mi355sw_config.flags (0x... accepted) */
     int getEngineVerbosity() const { return engineVerbosity; } /* --engine-verbosity=N: MI355SW_V_* bits (1 = messages, 2 = one line per partition, ...) */
     static void printGPUDevices(FILE* file);          /* --list-gpus (X/cuda_util.cpp:191-230) */
@@ -32,7 +33,7 @@ public:
     static int deviceWeights(int* weights, int max);  /* X/cuda_util.cpp:191-257: per-GPU weights, asked from a child process */
 
 private:
-    int gpu, waves, stripRows, blockColumns, pruneGlobal, noDiagonalSeed, wideAlphabet, engineFlags, engineVerbosity;
+    int gpu, waves, stripRows, blockColumns, pruneGlobal, noDiagonalSeed, wideAlphabet, int32PruneGlobal, engineFlags, engineVerbosity;
 };
 
 #endif

@@ -21,6 +21,9 @@ MI355X) behind the handful of MASA-CUDAlign options that concern the path -- not
                                 stage 1 resumes by itself
       --wide-alphabet           sequences with 15 to 62 letters in common (all IUPAC codes, ...) run on the packed kernels too
                                 (MI355SW_F_WIDE_ALPHABET; same alignment, off by default)
+      --int32-prune-global      with --prune-global: sequences that run on the int32 kernels (15 or more letters in common without
+                                --wide-alphabet, 63 or more with it, overflow reruns) prune a global alignment too
+                                (MI355SW_F_INT32_PRUNE_GLOBAL; same alignment, off by default)
 
 Prints one JSON line (best score, crosspoints per stage, seconds per stage) and leaves alignment.00.txt in the work
 directory.  The engine has no CPU fallback: without an MI355X this fails with MI355SW_ENOGPU."""
@@ -48,7 +51,7 @@ def main(argv):
             "+": pkg.AT_SEQUENCE_1_AND_2}
     work, limit, device, prune, only1, edges, count, ram = "./work.tmp", None, 0, True, False, "**", 1, 0
     trim, rev, comp, clear_n = [0, 0, 0, 0], [False, False], [False, False], False
-    prune_global = prune_traceback = wide_alphabet = prune_edges = False
+    prune_global = prune_traceback = wide_alphabet = prune_edges = int32_prune_global = False
     weights = None
     resume = False
     files = []
@@ -83,6 +86,8 @@ def main(argv):
             prune_edges = True
         elif a == "--wide-alphabet":
             wide_alphabet = True
+        elif a == "--int32-prune-global":
+            int32_prune_global = True
         elif a.startswith("--split="):
             v = [int(x) for x in a[8:].split(",")]
             weights = [1] * v[0] if len(v) == 1 else v
@@ -102,7 +107,8 @@ def main(argv):
                                                          trim_start=trim[2 * k], trim_end=trim[2 * k + 1])) for k in (0, 1)]
     if limit is None:
         limit = min((len(seqs[0]) // 8192 + 2) * (len(seqs[1]) + 1) * 8, 4 << 30)
-    al = pkg.MI355Aligner(device=device, flags=pkg.engine.F_WIDE_ALPHABET if wide_alphabet else 0)
+    al = pkg.MI355Aligner(device=device, flags=(pkg.engine.F_WIDE_ALPHABET if wide_alphabet else 0) |
+                          (pkg.engine.F_INT32_PRUNE_GLOBAL if int32_prune_global else 0))
     try:
         if only1:
             bounds = (seqs[0].offset0 - 1, seqs[1].offset0 - 1, seqs[0].offset1, seqs[1].offset1)
