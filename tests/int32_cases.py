@@ -30,7 +30,8 @@ BASE = 300                                               # length of the string 
 
 
 def letters(way):
-    return np.frombuffer(WAYS[way][0], dtype=np.uint8)
+    """the alphabet of a way of WAYS -- or, for callers with ways of their own (tests/packed_cases.py), the alphabet itself as bytes"""
+    return np.frombuffer(way if isinstance(way, bytes) else WAYS[way][0], dtype=np.uint8)
 
 
 def flags(way):
