@@ -160,12 +160,36 @@ typedef struct {
                                                the packed kernels.  A band of a chain (column ports, share_best) prunes against the distances to the
                                                end of the super-partition with its own finds and its own initial_bound; the running best of the other
                                                bands is not relayed to this family (the chain's words are in the packed kernels' domain).
-                                               NOT served, every cell computed as before: the edge rule (mi355sw_set_prune_end), goal bounds
-                                               (mi355sw_set_goal_bounds), reproducible pruning (MI355SW_F_DETERMINISTIC_PRUNE is ignored by this
+                                               NOT served by this flag, every cell computed as before: the edge rule (mi355sw_set_prune_end) and goal
+                                               bounds (mi355sw_set_goal_bounds) -- they have a flag of their own, MI355SW_F_INT32_PRUNE_EDGE_GOAL --,
+                                               reproducible pruning (MI355SW_F_DETERMINISTIC_PRUNE is ignored by this
                                                family), the partitions of mi355sw_align_partitions, and the diagonal seed -- it needs the packed
                                                kernels, so a caller hands a bound in through initial_bound (mi355sw_seed_bound makes one where the
                                                pair runs on the packed kernels).  No pruning window, fast-forward or retire: every strip walks the
                                                whole width. */
+#define MI355SW_F_INT32_PRUNE_EDGE_GOAL 262144 /* the EDGE rule (mi355sw_set_prune_end) and GOAL bounds (mi355sw_set_goal_bounds) on the int32 kernel family too
+                                               (additive in ABI 8; off by default: without it every run is what it was, such a request on the int32
+                                               kernels computes every cell).  A flag of its own: MI355SW_F_INT32_PRUNE_GLOBAL alone serves neither, and
+                                               this one alone leaves a last-cell request unpruned.  With it, a stream that runs on the int32 kernels
+                                               -- 15 or more common byte values (63 or more with MI355SW_F_WIDE_ALPHABET), MI355SW_F_FORCE_INT32, the
+                                               rerun after an MI355SW_EOVERFLOW16 report (mi355sw_align_partition keeps the edge and the bounds on that
+                                               attempt) -- takes
+                                               * the edge request under the packed kernels' conditions (NEEDLEMAN_WUNSCH, nothing tracked, prune_blocks,
+                                                 the border(s) the result is read from wanted, no batch, no block scores) at any rows_per_lane (12
+                                                 runs as 8, 24 / 32 as 16); a band of a chain keeps it and prunes against the distances to the end of
+                                                 the super-partition with its own finds and its own initial_bound (the chain's running best and
+                                                 mi355sw_stream_best_hint are not relayed to this family).  initial_bound starts the bound, no probe and
+                                                 no seed run, MI355SW_EBOUND is held against the best H of the named edge(s)
+                                                 (mi355sw_stats.kernel: sw_strip_kernel<R,false,..,false,true,false,true>);
+                                               * goal bounds for a NEEDLEMAN_WUNSCH partition with nothing tracked whose last column is handed out, no
+                                                 prune_blocks, no port, no share_best, at the strip height the family runs the partition at -- also each
+                                                 partition that mi355sw_align_partitions runs on a launch of its own (every pair this family serves),
+                                                 with its own bounds.  No probe, seed or bound; MI355SW_EBOUND does not apply
+                                                 (mi355sw_stats.kernel: sw_strip_kernel<R,false,..,false,true,true>).
+                                               The unit is one 64-step slab of a strip, skipped cells read H = E = F = -INF, pruned_cells +
+                                               processed_cells = m * n.  NOT served, every cell computed as before: MI355SW_F_DETERMINISTIC_PRUNE (with
+                                               it this family drops both requests; a saved pruning state stays refused), block_score_columns > 0, a
+                                               local recurrence, a tracking manager.  No pruning window, fast-forward or retire. */
 #define MI355SW_F_NO_HOST_COUNTER 512       /* the kernel does not mirror its strip counter into host memory (measurements) */
 #define MI355SW_V_MESSAGES 1                /* one line per noteworthy event (overflow reruns, the diagonal seed, ...) */
 #define MI355SW_V_JOBS 2                    /* timing of every mi355sw_align_partition job */
@@ -313,7 +337,8 @@ int mi355sw_align_partitions(mi355sw_handle* h, int32_t count, const mi355sw_par
  * it, is exact.  The bounds are constants, so which cells go is a function of the input.  Applies to NEEDLEMAN_WUNSCH partitions
  * with nothing tracked whose last column is dispatched, on the packed kernels at 256- / 512-row strips (rows_per_lane 4 / 8,
  * or 0: picked by the engine), in a batch at 256- / 1024-row strips; anything else -- more than 14 common byte values (more than 62 with MI355SW_F_WIDE_ALPHABET),
- * MI355SW_F_FORCE_INT32, an overflow rerun -- computes every cell.  No probe or seed runs and MI355SW_EBOUND does not apply
+ * MI355SW_F_FORCE_INT32, an overflow rerun -- computes every cell, unless MI355SW_F_INT32_PRUNE_EDGE_GOAL is set: the int32
+ * kernels then take the bounds on a launch of their own at any of their heights.  No probe or seed runs and MI355SW_EBOUND does not apply
  * (the bound is not the score of a last cell).  mi355sw_stats.pruned_cells / processed_cells / kernel report it. */
 int mi355sw_set_goal_bounds(mi355sw_handle* h, int32_t count, const int32_t* column_bounds, const int32_t* row_bounds);
 
@@ -332,8 +357,9 @@ int mi355sw_set_goal_bounds(mi355sw_handle* h, int32_t count, const int32_t* col
  * LAST_ROW, the last column for LAST_COLUMN, both for ROW_OR_COLUMN, on the packed kernels (one-hot or wide form) at 256-,
  * 512-, 1024- or 2048-row strips (rows_per_lane 4 / 8 / 16 / 32, or 0: the engine picks among them).  Anything else -- another
  * fixed height, MI355SW_F_FORCE_INT32, more than 14 common byte values without MI355SW_F_WIDE_ALPHABET, an overflow rerun, a
- * batch, a local recurrence, a tracking manager -- computes every cell: same result, pruned_cells == 0.  A
- * manager that dispatches the last cell keeps the last-cell rule.
+ * batch, a local recurrence, a tracking manager -- computes every cell: same result, pruned_cells == 0.  With
+ * MI355SW_F_INT32_PRUNE_EDGE_GOAL the int32 kernels take the request too (forced, the alphabet, an overflow rerun; any
+ * rows_per_lane), under the other conditions unchanged.  A manager that dispatches the last cell keeps the last-cell rule.
  * A BAND OF A CHAIN (first_column_port / last_column_port / share_best, or a first column the host streams in) keeps the
  * request: di and dj are the distances to the end of the SUPER-partition (prune_rows / prune_cols), so what every band folds
  * into the shared running best is a lower bound of the best H on the allowed edge of the whole matrix.  Every band holds a

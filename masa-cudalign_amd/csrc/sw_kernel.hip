@@ -204,6 +204,35 @@ __device__ __forceinline__ int nw_lower32(const int t, const long long kmax, con
     const long long lb = (long long) t - 3 * kmax - 3 - 2 * dmax;
     return lb > (long long) NEG_INF ? (int) lb : NEG_INF;
 }
+// EDGE (opt-in, MI355SW_F_INT32_PRUNE_EDGE_GOAL; KernelArgs::prune_end 1: the alignment ends anywhere on the last row, 2: anywhere
+// on the last column, 3: on either): edge_upper16 / edge_lower16 of sw_kernel_pk16.inc on int32 values with this family's spans.
+// Everything is the global rule's -- gbest a running lower bound, here of the best H on the named edge(s) minus GAP_FIRST; where
+// the bounds are folded; -INF for skipped cells; the clamps -- except the gap the rest of a path is forced to hold: to end on the
+// last row it only has to get DOWN, g = max(0, di - dj); on the last column ACROSS, g = max(0, dj - di); on either, none.
+__device__ __forceinline__ int edge_upper32(const int end, const int t, const int di, const int dj, const int si, const int sj) {
+    if (t <= NEG_INF / 2) return NEG_INF - 1;             // nothing enters here: below every lower bound, known or not
+    const int dlo = dj - sj - di, dhi = dj - di + si;      // range of (columns left - rows left) over the cells
+    const int gmin = min(end == 1 ? max(0, -dhi) : (end == 2 ? max(0, dlo) : 0), 400000000);   // the least forced gap among them
+    return t + min(di, dj) - 2 * gmin + NW32_PRUNE_MARGIN;
+}
+// mismatches down the diagonal to the nearer edge, at most `kmax` steps, and -- only where that edge is not one the alignment may
+// end on -- one gap along it; dlo .. dhi: range of (columns left - rows left) over the cells the maximum may lie in
+__device__ __forceinline__ int edge_lower32(const int end, const int t, const long long kmax, const long long dlo, const long long dhi) {
+    const long long gmax = end == 1 ? -dlo : (end == 2 ? dhi : 0);   // the largest forced gap among them
+    const long long lb = (long long) t - 3 * kmax - (gmax > 0 ? 3 + 2 * gmax : 0);
+    return lb > (long long) NEG_INF ? (int) lb : NEG_INF;
+}
+// GOAL (the same flag; KernelArgs::goal_bound_col / _row, t domain, constants of the sweep): goal_keep16 on int32 values.  A cell
+// that holds t with dj columns left reaches the last column with at most t + dj, and the last row with at most
+// t + min(di, dj) - 2 * (di - dj) when it has more rows left than columns.  `t` bounds cells whose rows-left lie in [di - si, di]
+// and whose columns-left are at most dj; a term that is off sits out of every value's reach.  (64-bit: t + dj need not fit.)
+__device__ __forceinline__ bool goal_keep32(const int t, const int di, const int dj, const int si, const long long gcol, const long long grow) {
+    if (t <= NEG_INF / 2) return false;                   // nothing enters here
+    const long long ucol = (long long) t + dj + NW32_PRUNE_MARGIN;
+    const long long surplus = (long long) di - si - dj;   // the least (rows left - columns left) among the cells
+    const long long urow = (long long) t + min(di, dj) - 2 * (surplus > 0 ? surplus : 0) + NW32_PRUNE_MARGIN;
+    return ucol >= gcol || urow >= grow;
+}
 // a lane's state at a chunk boundary, -INF images pulled back up to -INF (t domain: -INF - GAP_FIRST)
 template <int R>
 __device__ __forceinline__ void clamp_void32(LaneState<R>& st) {
@@ -213,9 +242,11 @@ __device__ __forceinline__ void clamp_void32(LaneState<R>& st) {
     st.tbot = max(st.tbot, NEG_INF - GAP_FIRST);
     st.fbot = max(st.fbot, NEG_INF);
 }
-template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false>
+template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false, bool GOAL = false, bool EDGE = false>
 __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, const int s_in, WaveLds* lds, const int lane) {
-    constexpr bool NWP = PRUNE && !SW;                  // the global (last-cell) rule
+    constexpr bool NWP = PRUNE && !SW;                  // the global (last-cell) rule, and its two variants:
+    static_assert(!GOAL || (PRUNE && !SW && !TRACK), "goal mode: global recurrence, pruning kernels, nothing tracked");
+    static_assert(!EDGE || (PRUNE && !SW && !TRACK && !GOAL), "edge mode: global recurrence, pruning kernels, nothing tracked, no goal");
     const UniformArgs a = uniform_args(ap);
     const int s = __builtin_amdgcn_readfirstlane(s_in);
     const int n = a->n;
@@ -288,6 +319,12 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
         for (int r = 0; r < R; r++) lane_entry = max(lane_entry, st.tl[r]);
     }
     const int pr_rows = PRUNE ? a->prune_rows - 1 - row0 : 0, pr_cols = PRUNE ? a->prune_cols - 1 : 0;
+    // goal mode: the two bounds, a term that is off (-INF in the argument block) out of every value's reach; edge mode: which edge(s)
+    const int goal_c = GOAL ? a->goal_bound_col : NEG_INF, goal_r = GOAL ? a->goal_bound_row : NEG_INF;
+    const long long gcol = goal_c <= NEG_INF / 2 ? 0x7fffffffffffffffll : (long long) goal_c;
+    const long long grow = goal_r <= NEG_INF / 2 ? 0x7fffffffffffffffll : (long long) goal_r;
+    const bool goal_any = goal_c > NEG_INF / 2 || goal_r > NEG_INF / 2;
+    const int prune_end = EDGE ? a->prune_end : 0;
 
     DBG(1, 1);
     // ---- sweep the strip ----
@@ -315,8 +352,22 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
                 code = a->seq1[col];
             }
             if (PRUNE) {
-                gseen = max(gseen, poll_agent(a->gbest_in));
-                if (NWP) {
+                if (!GOAL) gseen = max(gseen, poll_agent(a->gbest_in));     // (goal mode: the bounds are fixed, nothing is read)
+                if (GOAL) {
+                    if (!ragged && col0 >= 2 * CHUNK && col0 + CHUNK <= n) {
+                        // (the same two entries as below, held against the sweep's own bounds: see goal_keep32)
+                        const bool own = goal_keep32(lane_entry, pr_rows - lane * R, pr_cols - col0 + lane + 2, R - 1, gcol, grow);
+                        const bool top = goal_keep32(hf.x - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, gcol, grow);
+                        skip = goal_any && !__any(own || top);
+                    }
+                } else if (EDGE) {
+                    if (!ragged && col0 >= 2 * CHUNK && col0 + CHUNK <= n) {
+                        // (the same two entries and spans as below: see edge_upper32)
+                        const int own = edge_upper32(prune_end, lane_entry, pr_rows - lane * R, pr_cols - col0 + lane + 2, R - 1, 2);
+                        const int top = edge_upper32(prune_end, hf.x - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, 1);
+                        skip = !__any(max(own, top) >= gseen);
+                    }
+                } else if (NWP) {
                     if (!ragged && col0 >= 2 * CHUNK && col0 + CHUNK <= n) {
                         // what enters the slab: the lane's own last column (its R rows, column col0 - lane - 1, one column
                         // of room on either side) and the bus cell of its column (the row above the strip; its left
@@ -379,13 +430,14 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
                 clamp_void32<R>(st);
                 // what this slab's cells say about H[m][n] from below.  The lane's maximum is the score of one of its cells --
                 // its R rows, columns col0 - lane .. + 63 -- wherever it is: only slabs of full rows and columns are asked
+                // (edge mode: about the best H on the named edge(s); goal mode: the bounds are fixed, nothing is folded or published)
                 int lbv = NEG_INF;
-                if (!masked && !ragged) {
+                if (!GOAL && !masked && !ragged) {
                     const long long ki = (long long) pr_rows - lane * R, dj = (long long) pr_cols - col0 + lane;
                     const long long dhi = dj - (ki - (R - 1)), dlo = (dj - 63) - ki;
-                    lbv = nw_lower32(cm, ki < dj ? ki : dj, dhi > -dlo ? dhi : -dlo);
+                    lbv = EDGE ? edge_lower32(prune_end, cm, ki < dj ? ki : dj, dlo, dhi) : nw_lower32(cm, ki < dj ? ki : dj, dhi > -dlo ? dhi : -dlo);
                 }
-                if (__any(lbv > gseen)) {
+                if (!GOAL && __any(lbv > gseen)) {
                     int w = lbv;
 #pragma unroll
                     for (int d = 32; d >= 1; d >>= 1) w = max(w, __shfl_xor(w, d));
@@ -477,7 +529,7 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
 #ifndef SW32_WAVES_PER_SIMD
 #define SW32_WAVES_PER_SIMD 2
 #endif
-template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false>
+template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false, bool GOAL = false, bool EDGE = false>
 __global__ void __launch_bounds__(64)
 #if SW32_WAVES_PER_SIMD == 2
 __attribute__((amdgpu_waves_per_eu(R == 16 ? 1 : 2, R == 16 ? 1 : 2)))
@@ -506,7 +558,7 @@ sw_strip_kernel(const KernelArgs* __restrict__ ap) {
             __builtin_amdgcn_wave_barrier();
             break;
         } else {
-            process_strip<R, SW, PROFILE, TRACK, PRUNE>(ap, s, lds, lane);
+            process_strip<R, SW, PROFILE, TRACK, PRUNE, GOAL, EDGE>(ap, s, lds, lane);
         }
         complete_strip_common(ap, s, lane, 64 * R, true);
     }
@@ -534,12 +586,18 @@ __global__ void fill_cells_kernel(int2* p, long long count, int2 value) {
 }
 
 template <int R>
-static hipError_t launch_r(const KernelArgs* a, int grid, hipStream_t stream, bool sw, bool profile, bool track, bool prune) {
+static hipError_t launch_r(const KernelArgs* a, int grid, hipStream_t stream, bool sw, bool profile, bool track, bool prune, bool goal, bool edge) {
 #define LAUNCH(SWV, PRV, TRV) \
     hipLaunchKernelGGL((sw_strip_kernel<R, SWV, PRV, TRV>), dim3(grid), dim3(64), 0, stream, a)
     if (sw && prune) {        // block pruning: local alignments with their best score tracked
         if (profile) hipLaunchKernelGGL((sw_strip_kernel<R, true, true, true, true>), dim3(grid), dim3(64), 0, stream, a);
         else hipLaunchKernelGGL((sw_strip_kernel<R, true, false, true, true>), dim3(grid), dim3(64), 0, stream, a);
+    } else if (prune && goal) {   // ... global ones that look for a goal on their last column / row (MI355SW_F_INT32_PRUNE_EDGE_GOAL)
+        if (profile) hipLaunchKernelGGL((sw_strip_kernel<R, false, true, false, true, true>), dim3(grid), dim3(64), 0, stream, a);
+        else hipLaunchKernelGGL((sw_strip_kernel<R, false, false, false, true, true>), dim3(grid), dim3(64), 0, stream, a);
+    } else if (prune && edge) {   // ... global ones that end on an edge of the super-partition (the same flag)
+        if (profile) hipLaunchKernelGGL((sw_strip_kernel<R, false, true, false, true, false, true>), dim3(grid), dim3(64), 0, stream, a);
+        else hipLaunchKernelGGL((sw_strip_kernel<R, false, false, false, true, false, true>), dim3(grid), dim3(64), 0, stream, a);
     } else if (prune) {       // ... and global ones whose goal is the last cell, nothing tracked (MI355SW_F_INT32_PRUNE_GLOBAL)
         if (profile) hipLaunchKernelGGL((sw_strip_kernel<R, false, true, false, true>), dim3(grid), dim3(64), 0, stream, a);
         else hipLaunchKernelGGL((sw_strip_kernel<R, false, false, false, true>), dim3(grid), dim3(64), 0, stream, a);
@@ -562,10 +620,14 @@ hipError_t launch_strip_kernel(const KernelArgs& a, KernelArgs* dargs, int rows_
     if (e != hipSuccess) return e;
     // (the runtime sets a.prune for this family where an instantiation exists: local and tracked, or global and not tracked)
     const bool prune = a.prune != 0 && (sw ? track : !track);
+    // goal and edge mode, under the packed dispatch's conditions (launch_strip_kernel_pk16)
+    const bool goal = prune && (a.goal_bound_col > NEG_INF / 2 || a.goal_bound_row > NEG_INF / 2);
+    const bool edge = prune && !goal && a.prune_end != 0;
+    if ((goal || edge) && (track || sw)) return hipErrorInvalidValue;
     switch (rows_per_lane) {
-    case 4: return launch_r<4>(dargs, grid, stream, sw, profile, track, prune);
-    case 8: return launch_r<8>(dargs, grid, stream, sw, profile, track, prune);
-    case 16: return launch_r<16>(dargs, grid, stream, sw, profile, track, prune);
+    case 4: return launch_r<4>(dargs, grid, stream, sw, profile, track, prune, goal, edge);
+    case 8: return launch_r<8>(dargs, grid, stream, sw, profile, track, prune, goal, edge);
+    case 16: return launch_r<16>(dargs, grid, stream, sw, profile, track, prune, goal, edge);
     default: return hipErrorInvalidValue;
     }
 }
