@@ -15,14 +15,18 @@ reduced with BestScoreList's order.
 The compute engine is injected (`engine_factory`) so that the N>1 plumbing can be exercised on CPU
 with a stand-in; the product engine is MI355Aligner (HIP, no CPU fallback).
 """
+import json
 import os
 import sys
 import threading
 import time
+import zlib
 
 import numpy as np
 
-from .engine import INF, SMITH_WATERMAN, NEEDLEMAN_WUNSCH, INIT_WITH_ZEROES, INIT_WITH_GAPS, INIT_WITH_CUSTOM_DATA, Partition
+from . import sra as sra_mod
+from .engine import (INF, SMITH_WATERMAN, NEEDLEMAN_WUNSCH, INIT_WITH_ZEROES, INIT_WITH_GAPS, INIT_WITH_CUSTOM_DATA, Partition,
+                     AlignerError)
 
 
 def band_limits(n, weights):
@@ -88,7 +92,6 @@ def check_chain_bound(score, bound):
     an alignment that exists / a lower bound of H[m][n], and slabs that can still reach it are computed.  A chain that ends below
     was given a bound no alignment reaches -- its optimum may have been pruned away, the result is void.  One stream checks this
     itself (MI355SW_EBOUND, mi355sw_stream_end); a band of a chain cannot (the best may be another band's)."""
-    from .engine import AlignerError
     if bound is not None and score is not None and int(score) < int(bound):
         raise AlignerError("EBOUND: the chain ended at %d, below the bound %d its pruning started from -- no alignment reaches that "
                            "bound, the result is void" % (int(score), int(bound)))
@@ -112,6 +115,79 @@ def check_prune_end(prune_end, recurrence, track_best):
         raise ValueError("prune_end %r is none of 0 (the last cell / the best cell), 1 (last row), 2 (last column), 3 (either)" % (prune_end,))
     if prune_end and (recurrence != NEEDLEMAN_WUNSCH or track_best):
         raise ValueError("prune_end=%d needs recurrence=NEEDLEMAN_WUNSCH and track_best=False" % prune_end)
+
+
+def _border_h(init_type, k):
+    """H of the cell at distance k from the origin on a generated first row or column: 0 on a border of zeroes and in the
+    origin itself, else k gap extensions and, for INIT_WITH_GAPS, the gap's opening"""
+    if init_type == INIT_WITH_ZEROES or k == 0:
+        return 0
+    return -2 * k - (3 if init_type == INIT_WITH_GAPS else 0)
+
+
+def _corner_cell(first_row_init_type, j):
+    """(H, E) of DP cell (0, j) on the first row: the corner of the band that starts at column j.  Zero-initialised rows give
+    (0,-INF); custom rows are handled by the caller feeding row 0 of the stream."""
+    return np.array([[_border_h(first_row_init_type, j), -INF]], dtype=np.int32)
+
+
+def _stop_stream(engine, swallow, guard_abort=True):
+    """stops an open stream: the kernel is aborted, then the stream ended.  A failure of either that is of the classes `swallow`
+    is dropped (there is no stream any more: the path that raised has ended it already) -- with guard_abort=False only
+    streamEnd's, streamAbort's reaches the caller and the stream is not ended."""
+    for fn, guarded in ((engine.streamAbort, guard_abort), (engine.streamEnd, True)):
+        try:
+            fn()
+        except swallow:
+            if not guarded:
+                raise
+
+
+def _edges_held(prune_end, last):
+    """the edge cells of the whole matrix that a band holds, as prune_end's bits: its slice of the last row, and -- the last
+    band -- the last column"""
+    return (prune_end & 1) | ((prune_end & 2) if last else 0)
+
+
+def _arm_prune_end(engine, prune_end, prune_blocks):
+    """with block pruning the engine hears of the edge before EVERY streamBegin (the int32 retry too: the engine then drops it
+    together with the pruning)"""
+    if prune_end and prune_blocks:
+        engine.setPruneEnd(prune_end)
+
+
+def _seed_bound(engine, m, n, recurrence, prune_end, first_row_init_type, first_col_init_type):
+    """the diagonal seed of the whole m x n matrix for a pruning chain: the edge form's where the alignment ends on an edge"""
+    if prune_end:
+        return edge_seed_bound(engine, m, n, first_row_init_type, first_col_init_type)
+    return chain_seed_bound(engine, m, n, recurrence, first_row_init_type, first_col_init_type)
+
+
+def _stream_keywords(m, j0, n, first, last, port, chain, recurrence, track_best, first_row_init_type, first_col_init_type,
+                     prune_end, prune, want_last_row, force_int32):
+    """streamBegin's keywords for the band that starts at column j0 of an n-column matrix and runs m rows.  first / last: its
+    place in the chain; port: the boundary columns travel through column ports (else through the host, in segments); chain:
+    there is more than one band; prune: block pruning is on for this recurrence."""
+    kw = dict(recurrence_type=recurrence, track_best=track_best,
+              first_row_init_type=first_row_init_type, first_row_start_offset=j0,
+              want_last_column=((not last) and not port) or bool(_edges_held(prune_end, last) & 2),
+              last_column_port=(not last) and port,
+              want_last_row=want_last_row or bool(prune_end & 1), force_int32=force_int32)
+    if prune:
+        # every band prunes against the best of the whole chain (share_best) and bounds the gain still possible
+        # by the extents of the whole matrix, not of its own band
+        kw.update(prune_blocks=True, prune_rows=m, prune_cols=n - j0, share_best=chain)
+    if first:
+        kw.update(first_column_init_type=first_col_init_type)
+    else:
+        kw.update(first_column_init_type=INIT_WITH_CUSTOM_DATA, first_column=_corner_cell(first_row_init_type, j0),
+                  stream_first_column=not port, first_column_port=port)
+    return kw
+
+
+def _start_token(ok, bound):
+    import torch
+    return torch.tensor([1 if ok else 0, NO_BOUND if bound is None else int(bound)], dtype=torch.int64)
 
 
 class BandRunner:
@@ -230,7 +306,6 @@ class BandRunner:
         switches all ranks to transport="host"."""
         if self.transport != "p2p":
             return True
-        from .engine import AlignerError
         # the check's time budget: the engine's in-kernel waits (mi355sw_config.wait_seconds) and this driver's stall limit
         saved_wait, saved_stall, saved_prune = self.engine._opts["wait_seconds"], self.stall_abort_s, self.prune_blocks
         self.engine.configure(wait_seconds=budget_s)
@@ -250,11 +325,7 @@ class BandRunner:
                 except Exception as e:          # a wait that ran out, a stalled band, a refused mapping
                     self.p2p_error = "%s run of the transport check: %s" % (transport, e)
                     ok = 0
-                    for fn in (self.engine.streamAbort, self.engine.streamEnd):
-                        try:
-                            fn()
-                        except (AlignerError, AttributeError):
-                            pass
+                    _stop_stream(self.engine, (AlignerError, AttributeError))
                 if all_min(ok) == 0:
                     return False
             same = 1 if got["p2p"] == got["host"] else 0
@@ -270,34 +341,10 @@ class BandRunner:
             except AlignerError:            # (a stream the check left active: the caller closes the engine)
                 self.engine._opts["wait_seconds"] = saved_wait
 
-    def run(self, *args, **kwargs):
-        """_run (below) with the stream cleaned up behind it: whatever ends the run once its stream has begun -- an engine error,
-        an exception out of `special_row_sink` or out of the link to the next band, a stalled chain -- the kernel is stopped
-        (streamAbort) and the stream ended before the exception travels on, so the engine takes the next streamBegin."""
-        self._stream_open = False
-        self._rx_stop = threading.Event()
-        self._bx_stop = self._rx = None
-        try:
-            return self._run(*args, **kwargs)
-        except BaseException:
-            self._rx_stop.set()
-            if self._bx_stop is not None:
-                self._bx_stop.set()
-            if self._rx is not None:            # (a receiver in the middle of a feed finishes it before the stream goes)
-                self._rx.join(timeout=5.0)
-            if self._stream_open:
-                self._stream_open = False
-                for fn in (self.engine.streamAbort, self.engine.streamEnd):
-                    try:
-                        fn()
-                    except Exception:           # (no stream any more: the path that raised has ended it already)
-                        pass
-            raise
-
-    def _run(self, m, j0, j1, recurrence=SMITH_WATERMAN, track_best=True, first_row_init_type=INIT_WITH_ZEROES,
-             first_col_init_type=INIT_WITH_ZEROES, poll_sleep=0.0005, want_last_row=False, before_end=None,
-             force_int32=False, digest_inbound=False, special_row_interval=0, special_row_sink=None, n_total=None,
-             keep_inbound=False, prune_end=0, row0=0, first_row=None, inbound_prefix=None, initial_bound=None):
+    def run(self, m, j0, j1, recurrence=SMITH_WATERMAN, track_best=True, first_row_init_type=INIT_WITH_ZEROES,
+            first_col_init_type=INIT_WITH_ZEROES, poll_sleep=0.0005, want_last_row=False, before_end=None,
+            force_int32=False, digest_inbound=False, special_row_interval=0, special_row_sink=None, n_total=None,
+            keep_inbound=False, prune_end=0, row0=0, first_row=None, inbound_prefix=None, initial_bound=None):
         """seq1 of the engine must already hold the whole horizontal sequence (or at least [j0,j1)).
         digest_inbound: leave the crc32 of the boundary column this band received in self.inbound_crc (host transport:
         the segments as they arrive; p2p: the port's memory, read back once the band is through).
@@ -323,352 +370,22 @@ class BandRunner:
         at row r, special rows come on the grid of the whole band and reach the sink with their row of the whole band, and
         pruning counts m - r rows to the end of the matrix.
         initial_bound: the bound the FIRST band's pruning starts from in place of the diagonal seed (the bound a resumed chain
-        started from); the other bands hear theirs from the left."""
-        import zlib
-        from .engine import AlignerError
-        check_prune_end(prune_end, recurrence, track_best)
-        self.edge_best = None
-        self.inbound_crc = 0 if digest_inbound else None
-        eng, dist = self.engine, self.dist
-        first, last = self.rank == 0, self.rank == self.world - 1
-        self.inbound_column = np.empty((m + 1, 2), dtype=np.int32) if (keep_inbound and not first) else None
-        p2p = self.transport == "p2p"
-        row0 = int(row0)
-        if row0:
-            if not 0 < row0 < m or first_row is None or p2p or (not first and inbound_prefix is None):
-                raise ValueError("run(row0=%d): a row inside the band, its first row, the inbound column above it, no column port" % row0)
-        part = Partition(row0, j0, m, j1)
-        m_all, m = m, m - row0           # from here on m counts the rows of the partition; the engine's rows are relative to row0
-        seg = self.segment_rows
-        nseg = (m + seg - 1) // seg
-        # local alignments prune against the chain's running best score; global ones (NEEDLEMAN_WUNSCH with nothing tracked:
-        # the answer is the last cell of the last band) against a running lower bound of that cell, AbstractBlockPruning.cpp:92-109
-        prune = bool(self.prune_blocks and (track_best if recurrence == SMITH_WATERMAN else not track_best))
-        edges_here = (prune_end & 1) | ((prune_end & 2) if last else 0)      # the edge cells this band holds
-        kw = dict(recurrence_type=recurrence, track_best=track_best,
-                  first_row_init_type=first_row_init_type, first_row_start_offset=j0,
-                  want_last_column=((not last) and not p2p) or bool(edges_here & 2), last_column_port=(not last) and p2p,
-                  want_last_row=want_last_row or bool(prune_end & 1), force_int32=force_int32)
-        arm = (lambda: eng.setPruneEnd(prune_end)) if (prune_end and self.prune_blocks) else (lambda: None)
-        if special_row_interval > 0:
-            kw.update(special_row_interval=int(special_row_interval))
-        if prune:
-            # every band prunes against the best of the whole chain (share_best) and bounds the gain still possible
-            # by the extents of the whole matrix, not of its own band
-            kw.update(prune_blocks=True, prune_rows=m, prune_cols=(n_total if n_total is not None else j1) - j0,
-                      share_best=self.world > 1)
-        if row0:
-            # the rest of the band: DP row row0 as it was saved is the first row, its leading cell the boundary column's
-            kw.update(first_row_init_type=INIT_WITH_CUSTOM_DATA, first_row=np.ascontiguousarray(first_row, dtype=np.int32))
-        if first:
-            kw.update(first_column_init_type=first_col_init_type)
-            if row0:
-                kw.update(first_column_start_offset=row0)
-        else:
-            # corner cell = first-row cell at column j0-1+1 ... (H of DP cell (0, j0)): zero-initialised
-            # rows give (0,-INF); custom rows are handled by the caller feeding row 0 of the stream.
-            corner = np.array([[0, -INF]], dtype=np.int32)
-            if first_row_init_type != INIT_WITH_ZEROES:
-                open_ = 3 if first_row_init_type == 1 else 0
-                corner[0, 0] = -2 * j0 - open_ if j0 > 0 else 0
-            if row0:
-                prefix = np.asarray(inbound_prefix, dtype=np.int32).reshape(-1, 2)
-                if len(prefix) != row0 + 1:
-                    raise ValueError("run(row0=%d): inbound_prefix holds %d cells, not %d" % (row0, len(prefix), row0 + 1))
-                if self.inbound_column is not None:
-                    self.inbound_column[:row0 + 1] = prefix
-                corner = prefix[row0:row0 + 1].copy()
-            kw.update(first_column_init_type=INIT_WITH_CUSTOM_DATA, first_column=corner,
-                      stream_first_column=not p2p, first_column_port=p2p)
-            if self.inbound_column is not None and not row0:
-                self.inbound_column[0] = corner[0]
-        if p2p:
-            self._exchange_ports(m)
-        # Ordered start: band g+1 launches its kernel only after band g has launched its own.  It could do nothing
-        # before band g's first strip is through anyway, and where bands SHARE a GPU (tests and rehearsals on a
-        # one-GPU box) a kernel that sits polling for its neighbour has been seen to keep that neighbour's set-up
-        # work (fills, the seed pass) off the GPU for tens of seconds.
-        # The token always travels, whatever happens to this band's own start: 1 = started, 0 = failed (no memory for the
-        # special rows, a port that is not there) -- a band that never hears from its left neighbour would sit in recv
-        # with no kernel running and nothing for the stall watchdog to see, and so would every band to its right.
-        # With the token travels what the pruning bound starts from: band 0 runs the diagonal seed pass of the WHOLE matrix
-        # before it starts (the bands to its right could not start earlier anyway) and every band begins with that value.
-        def token(ok, bound):
-            import torch
-            return torch.tensor([1 if ok else 0, NO_BOUND if bound is None else int(bound)], dtype=torch.int64)
-
-        bound = None
-        if not first and dist is not None:
-            go = token(False, None)
-            dist.recv(go, src=self.rank - 1)
-            if int(go[0]) != 1:
-                if not last:
-                    dist.send(token(False, None), dst=self.rank + 1)
-                raise RuntimeError("band %d/%d: a band to the left failed to start its kernel" % (self.rank, self.world))
-            bound = None if int(go[1]) == NO_BOUND else int(go[1])
+        started from); the other bands hear theirs from the left.
+        The stream is cleaned up behind the run: whatever ends it once its stream has begun -- an engine error, an exception
+        out of `special_row_sink` or out of the link to the next band, a stalled chain -- the kernel is stopped (streamAbort)
+        and the stream ended before the exception travels on, so the engine takes the next streamBegin."""
+        job = _BandRun(self, poll_sleep, before_end, digest_inbound, special_row_interval, special_row_sink)
         try:
-            if first and initial_bound is not None:
-                bound = int(initial_bound)
-            elif first and prune and self.seed_bound and self.world > 1 and n_total is not None:
-                if prune_end:
-                    bound = edge_seed_bound(eng, m_all, n_total, first_row_init_type, first_col_init_type)
-                else:
-                    bound = chain_seed_bound(eng, m_all, n_total, recurrence, first_row_init_type, first_col_init_type)
-            if prune and bound is not None:
-                kw.update(initial_bound=bound)
-            self.initial_bound = bound
-            arm()
-            eng.streamBegin(part, **kw)
-            self._stream_open = True
+            job.plan(m, j0, j1, recurrence, track_best, first_row_init_type, first_col_init_type, want_last_row, force_int32,
+                     n_total, keep_inbound, prune_end, row0, first_row, inbound_prefix)
+            job.start(initial_bound)
+            job.find_special_rows()
+            job.start_side_threads()
+            job.poll()
+            return job.finish()
         except BaseException:
-            if not last and dist is not None:
-                dist.send(token(False, None), dst=self.rank + 1)
+            job.stop()
             raise
-        if not last and dist is not None:
-            dist.send(token(True, bound), dst=self.rank + 1)
-        self.restarts = 0
-
-        lock = threading.Lock()          # the engine handle is driven by one thread at a time
-        errors = []
-        fed = [0]                        # rows of the inbound column handed to the engine so far (host transport)
-
-        def receiver():
-            # inbound boundary column: blocking recv of row segments from the left neighbour
-            try:
-                for q in range(nseg):
-                    r0 = q * seg
-                    ln = min(seg, m - r0)
-                    buf = self._tensor(ln)
-                    dist.recv(buf, src=self.rank - 1)
-                    if self._rx_stop.is_set():         # the run has ended (run's clean-up): nothing more goes to the engine
-                        return
-                    if digest_inbound:
-                        self.inbound_crc = zlib.crc32(buf.numpy().tobytes(), self.inbound_crc)
-                    a0 = row0 + r0                     # the segment's first row in the whole band
-                    if self.inbound_column is not None:
-                        self.inbound_column[a0 + 1:a0 + ln + 1] = buf.numpy()
-                    if inbound_h is not None:          # H of the boundary column at every possible special row
-                        q0 = a0 // 256 + 1
-                        q1 = (a0 + ln) // 256
-                        if q1 >= q0:
-                            inbound_h[q0:q1 + 1] = buf.numpy()[q0 * 256 - 1 - a0:q1 * 256 - a0:256, 0]
-                    with lock:
-                        eng.streamFeedColumn(r0, buf.numpy())
-                        fed[0] = r0 + ln
-            except BaseException as e:     # surfaced by the main loop
-                errors.append(e)
-
-        def restart_int32():
-            """the packed kernel left its exact range: everything handed out so far is exact (the engine only
-            reports rows below the failing strip), so the band starts again on the int32 kernel and REPLAYS --
-            the inbound rows already received are still in the engine's column (pinned, or the port), outbound
-            segments already sent are not sent again (a port is simply written again with the same cells)."""
-            try:
-                eng.streamAbort()
-            except AlignerError:
-                pass
-            try:
-                eng.streamEnd()
-            except AlignerError:
-                pass
-            kw2 = dict(kw, force_int32=True)
-            if not first and not p2p:
-                kw2["first_column_resume_rows"] = fed[0]
-            arm()
-            eng.streamBegin(part, **kw2)
-            self.restarts += 1
-            reprobe_special()
-
-        # special rows of this band: DP rows (multiples of the strip height, AbstractDiagonalAligner::isSpecialRow)
-        # (special rows sit on multiples of the strip height, every strip height is a multiple of 256: the boundary
-        #  column's H at every 256th row covers whatever geometry a restart on the int32 kernels picks)
-        special_dp, special_next = [], [0]
-        inbound_h = np.zeros(m_all // 256 + 2, dtype=np.int32) if (special_row_interval > 0 and not first and not p2p) else None
-        if special_row_interval > 0:
-            while True:
-                try:
-                    dp, _ = eng.streamReadSpecialRow(len(special_dp), 0, 0)
-                except (AlignerError, IndexError):
-                    break
-                special_dp.append(int(dp))
-        self.special_rows = []
-
-        def reprobe_special():
-            """after a restart on the int32 kernels (other strip heights): the rows already handed over stay, the rest
-            are where the new geometry puts them"""
-            if special_row_interval <= 0:
-                return
-            done_to = self.special_rows[-1] if self.special_rows else 0
-            del special_dp[:]
-            while True:
-                try:
-                    dp, _ = eng.streamReadSpecialRow(len(special_dp), 0, 0)
-                except (AlignerError, IndexError):
-                    break
-                special_dp.append(int(dp))
-            special_next[0] = sum(1 for dp in special_dp if row0 + dp <= done_to)
-
-        def flush_special(rows_ok):
-            """hands over every special row whose strip is complete; called with the lock held"""
-            while special_next[0] < len(special_dp) and special_dp[special_next[0]] <= rows_ok:
-                k, dp = special_next[0], special_dp[special_next[0]]
-                if not first and not p2p and fed[0] < dp:
-                    return                                  # its boundary cell is still on the way
-                _, cells = eng.streamReadSpecialRow(k)
-                dpa = row0 + dp                             # the row in the whole band
-                if first:
-                    c0 = np.array([0 if first_col_init_type == INIT_WITH_ZEROES
-                                   else -2 * dpa - (3 if first_col_init_type == 1 else 0), -INF], dtype=np.int32)
-                elif p2p:
-                    c0 = np.array([int(eng.portRead(dp - 1, 1)[0, 0]), -INF], dtype=np.int32)
-                else:
-                    c0 = np.array([int(inbound_h[dpa // 256]), -INF], dtype=np.int32)
-                if special_row_sink is not None:
-                    special_row_sink(dpa, c0, cells)
-                self.special_rows.append(dpa)
-                special_next[0] += 1
-
-        # host transport: the chain's running best travels between the rank processes (p2p: between the kernels)
-        self.hints = 0
-        bx_stop, bx = threading.Event(), None
-        self._bx_stop = bx_stop          # (run's clean-up sets it too)
-        if prune and self.world > 1 and not p2p and self._best_group is not None:
-            def best_exchange():
-                import torch
-                known = -INF
-                try:
-                    while True:
-                        mine = eng.streamRunningBest() if not bx_stop.is_set() else -INF
-                        t = torch.tensor([max(mine, known), -1 if bx_stop.is_set() else 0], dtype=torch.int64)
-                        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self._best_group)
-                        if int(t[0]) > known:
-                            known = int(t[0])
-                            if known > mine and not bx_stop.is_set():
-                                try:
-                                    eng.streamBestHint(known)
-                                    self.hints += 1
-                                except AlignerError:
-                                    pass
-                        if int(t[1]) == -1:                  # every band is through
-                            return
-                        time.sleep(0.002)
-                except BaseException as e:
-                    errors.append(e)
-            bx = threading.Thread(target=best_exchange, daemon=True)
-            bx.start()
-
-        rx = None
-        if not first and not p2p:
-            rx = self._rx = threading.Thread(target=receiver, daemon=True)
-            rx.start()
-        send_q = 0
-        # a chain that stands still says where: one line per 10 s without progress on this band (rows completed,
-        # segments sent), one per second with MI355SW_BAND_DEBUG=1; after MI355SW_BAND_STALL_S seconds (default
-        # 900) without progress the band gives up instead of hanging its neighbours for ever
-        debug = os.environ.get("MI355SW_BAND_DEBUG") == "1"
-        stall_abort = self.stall_abort_s if self.stall_abort_s is not None else float(os.environ.get("MI355SW_BAND_STALL_S", "900"))
-        t_dbg = t_prog = time.time()
-        seen = (-1, -1)
-        rows_done, fin = 0, False
-        while True:
-            now = time.time()
-            if now - t_dbg >= (1.0 if debug else 10.0):
-                t_dbg = now
-                if (rows_done, send_q) != seen:
-                    seen, t_prog = (rows_done, send_q), now
-                if debug or now - t_prog >= 10.0:
-                    sys.stderr.write("[band %d/%d] rows_done=%d/%d finished=%d segments_sent=%d/%d no progress for %.0f s\n"
-                                     % (self.rank, self.world, rows_done, m, int(fin), send_q, nseg, now - t_prog))
-                    sys.stderr.flush()
-                if now - t_prog >= stall_abort:
-                    errors.append(RuntimeError("band %d/%d: no progress for %.0f s (rows_done=%d/%d, segments_sent=%d/%d)"
-                                               % (self.rank, self.world, now - t_prog, rows_done, m, send_q, nseg)))
-            if errors:
-                bx_stop.set()
-                with lock:
-                    eng.streamAbort()
-                    try:
-                        eng.streamEnd()
-                    except AlignerError:
-                        pass
-                    self._stream_open = False
-                if bx is not None:           # (it leaves its loop at the next all_reduce in which every band has said stop)
-                    bx.join(timeout=5.0)
-                raise errors[0]
-            with lock:
-                try:
-                    rows_done, fin = eng.streamPoll()
-                except AlignerError as e:
-                    if "EOVERFLOW16" not in str(e) or kw.get("force_int32") or self.restarts > 0:
-                        raise
-                    if os.environ.get("MI355SW_VERBOSE"):
-                        print("[bands] band %d/%d restarts on the int32 kernels: %s" % (self.rank, self.world, e), file=sys.stderr)
-                    restart_int32()
-                    continue
-                # (device-resident rows are read through the copy stream: only once nothing more has to be fed, so that
-                #  a copy held up behind the running kernel cannot starve that kernel of its first column)
-                if special_dp and (first or p2p or fed[0] >= m or fin):
-                    flush_special(rows_done)
-            progressed = False
-            # outbound boundary column (host transport): every complete segment goes to the right neighbour
-            while not last and not p2p and send_q < nseg:
-                r0 = send_q * seg
-                ln = min(seg, m - r0)
-                if rows_done < r0 + ln:
-                    break
-                buf = self._tensor(ln)
-                with lock:
-                    import torch
-                    buf.copy_(torch.from_numpy(eng.streamReadColumn(r0, ln)))
-                dist.send(buf, dst=self.rank + 1)
-                send_q += 1
-                progressed = True
-            if fin and (last or p2p or send_q >= nseg):
-                break
-            if not progressed:
-                time.sleep(poll_sleep)
-        if rx is not None:
-            rx.join()
-        if special_dp:
-            with lock:
-                flush_special(m)
-        if digest_inbound and p2p and not first:
-            self.inbound_crc = zlib.crc32(np.ascontiguousarray(eng.portRead(0, m), dtype=np.int32).tobytes())
-        if self.inbound_column is not None and p2p:
-            self.inbound_column[1:] = eng.portRead(0, m)
-        if edges_here:
-            self.edge_best = tuple(int(x) for x in eng.streamEdgeBest(edges_here))
-        if before_end is not None:       # e.g. read this band's slice of the last row while the stream is open
-            before_end(eng)
-        bx_stop.set()                   # the exchange thread keeps answering the other bands until every band is through
-        try:
-            best, _ = eng.streamEnd()
-        except AlignerError as e:        # e.g. reported by the exact-position pass of a very tall band
-            if "EOVERFLOW16" not in str(e) or kw.get("force_int32") or self.restarts > 0:
-                raise
-            with lock:
-                kw2 = dict(kw, force_int32=True)
-                if not first and not p2p:
-                    kw2["first_column_resume_rows"] = fed[0]
-                arm()
-                eng.streamBegin(part, **kw2)
-                self.restarts += 1
-            while True:
-                rows_done, fin = eng.streamPoll()
-                if fin:
-                    break
-                time.sleep(poll_sleep)
-            if edges_here:
-                self.edge_best = tuple(int(x) for x in eng.streamEdgeBest(edges_here))
-            if before_end is not None:
-                before_end(eng)
-            best, _ = eng.streamEnd()
-        self._stream_open = False
-        if bx is not None:
-            bx.join()
-        if errors:
-            raise errors[0]
-        return best
 
     def reduce_best(self, best):
         """global best = canonical max over bands (reference: relay through AlignerPool files)."""
@@ -688,6 +405,361 @@ class BandRunner:
         canonical maximum (score desc, i asc, j asc) over the bands' edge_best -- what Stage1Manager.getBestScore() gives for
         the same form on one partition, as a 0-based cell.  Collective.  A pruning chain is held to the bound it started from."""
         return self.reduce_best(self.edge_best if self.edge_best is not None else (-1, -1, -INF))
+
+
+class _BandRun:
+    """One BandRunner.run(): what its steps and its two side threads share, and the steps, in the order run() takes them.
+    stop() is run()'s clean-up when one of them raises."""
+
+    def __init__(self, runner, poll_sleep, before_end, digest_inbound, special_row_interval, special_row_sink):
+        self.runner, self.eng, self.dist = runner, runner.engine, runner.dist
+        self.rank, self.world = runner.rank, runner.world
+        self.first, self.last = runner.rank == 0, runner.rank == runner.world - 1
+        self.p2p = runner.transport == "p2p"
+        self.host_fed = not self.first and not self.p2p      # the inbound column arrives in row segments, through the host
+        self.poll_sleep, self.before_end, self.digest_inbound = poll_sleep, before_end, digest_inbound
+        self.interval, self.sink = special_row_interval, special_row_sink
+        self.lock = threading.Lock()     # the engine handle is driven by one thread at a time
+        self.errors = []                 # what ended a side thread; surfaced by the poll loop
+        self.fed = 0                     # rows of the inbound column handed to the engine so far (host transport)
+        self.special_dp, self.special_next = [], 0       # DP rows of the engine's special rows; the next one to hand over
+        self.inbound_h = None
+        self.send_q = 0                  # outbound segments sent so far
+        self.rx_stop, self.bx_stop = threading.Event(), threading.Event()
+        self.rx = self.bx = None
+        self.stream_open = False
+
+    # -- validate and plan -------------------------------------------------------------------------------------
+    def plan(self, m, j0, j1, recurrence, track_best, first_row_init_type, first_col_init_type, want_last_row, force_int32,
+             n_total, keep_inbound, prune_end, row0, first_row, inbound_prefix):
+        runner = self.runner
+        check_prune_end(prune_end, recurrence, track_best)
+        runner.edge_best = None
+        runner.inbound_crc = 0 if self.digest_inbound else None
+        runner.inbound_column = np.empty((m + 1, 2), dtype=np.int32) if (keep_inbound and not self.first) else None
+        row0 = int(row0)
+        if row0 and (not 0 < row0 < m or first_row is None or self.p2p or (not self.first and inbound_prefix is None)):
+            raise ValueError("run(row0=%d): a row inside the band, its first row, the inbound column above it, no column port" % row0)
+        self.part = Partition(row0, j0, m, j1)
+        self.row0, self.m_all, self.m = row0, m, m - row0     # m counts the rows of the partition; the engine's rows are relative to row0
+        self.seg = runner.segment_rows
+        self.nseg = (self.m + self.seg - 1) // self.seg
+        # local alignments prune against the chain's running best score; global ones (NEEDLEMAN_WUNSCH with nothing tracked:
+        # the answer is the last cell of the last band) against a running lower bound of that cell, AbstractBlockPruning.cpp:92-109
+        self.prune = bool(runner.prune_blocks and (track_best if recurrence == SMITH_WATERMAN else not track_best))
+        self.prune_end, self.edges_here = prune_end, _edges_held(prune_end, self.last)
+        self.recurrence, self.n_total = recurrence, n_total
+        self.first_row_init_type, self.first_col_init_type = first_row_init_type, first_col_init_type
+        kw = _stream_keywords(self.m, j0, n_total if n_total is not None else j1, self.first, self.last, self.p2p, self.world > 1,
+                              recurrence, track_best, first_row_init_type, first_col_init_type, prune_end, self.prune,
+                              want_last_row, force_int32)
+        if self.interval > 0:
+            kw.update(special_row_interval=int(self.interval))
+            if self.host_fed:
+                # (special rows sit on multiples of the strip height, every strip height is a multiple of 256: the boundary
+                #  column's H at every 256th row covers whatever geometry a restart on the int32 kernels picks)
+                self.inbound_h = np.zeros(m // 256 + 2, dtype=np.int32)
+        if row0:
+            # the rest of the band: DP row row0 as it was saved is the first row, its leading cell the boundary column's
+            kw.update(first_row_init_type=INIT_WITH_CUSTOM_DATA, first_row=np.ascontiguousarray(first_row, dtype=np.int32))
+            if self.first:
+                kw.update(first_column_start_offset=row0)
+            else:
+                prefix = np.asarray(inbound_prefix, dtype=np.int32).reshape(-1, 2)
+                if len(prefix) != row0 + 1:
+                    raise ValueError("run(row0=%d): inbound_prefix holds %d cells, not %d" % (row0, len(prefix), row0 + 1))
+                if runner.inbound_column is not None:
+                    runner.inbound_column[:row0 + 1] = prefix
+                kw.update(first_column=prefix[row0:row0 + 1].copy())
+        elif runner.inbound_column is not None:
+            runner.inbound_column[0] = kw["first_column"][0]
+        self.kw = kw
+
+    # -- ordered start -----------------------------------------------------------------------------------------
+    def start(self, initial_bound):
+        """Ordered start: band g+1 launches its kernel only after band g has launched its own.  It could do nothing
+        before band g's first strip is through anyway, and where bands SHARE a GPU (tests and rehearsals on a
+        one-GPU box) a kernel that sits polling for its neighbour has been seen to keep that neighbour's set-up
+        work (fills, the seed pass) off the GPU for tens of seconds.
+        The token always travels, whatever happens to this band's own start: 1 = started, 0 = failed (no memory for the
+        special rows, a port that is not there) -- a band that never hears from its left neighbour would sit in recv
+        with no kernel running and nothing for the stall watchdog to see, and so would every band to its right.
+        With the token travels what the pruning bound starts from: band 0 runs the diagonal seed pass of the WHOLE matrix
+        before it starts (the bands to its right could not start earlier anyway) and every band begins with that value."""
+        runner, dist, first, last = self.runner, self.dist, self.first, self.last
+        if self.p2p:
+            runner._exchange_ports(self.m)
+        bound = None
+        if not first and dist is not None:
+            go = _start_token(False, None)
+            dist.recv(go, src=self.rank - 1)
+            if int(go[0]) != 1:
+                if not last:
+                    dist.send(_start_token(False, None), dst=self.rank + 1)
+                raise RuntimeError("band %d/%d: a band to the left failed to start its kernel" % (self.rank, self.world))
+            bound = None if int(go[1]) == NO_BOUND else int(go[1])
+        try:
+            if first and initial_bound is not None:
+                bound = int(initial_bound)
+            elif first and self.prune and runner.seed_bound and self.world > 1 and self.n_total is not None:
+                bound = _seed_bound(self.eng, self.m_all, self.n_total, self.recurrence, self.prune_end,
+                                    self.first_row_init_type, self.first_col_init_type)
+            if self.prune and bound is not None:
+                self.kw.update(initial_bound=bound)
+            runner.initial_bound = bound
+            self.begin(self.kw)
+        except BaseException:
+            if not last and dist is not None:
+                dist.send(_start_token(False, None), dst=self.rank + 1)
+            raise
+        if not last and dist is not None:
+            dist.send(_start_token(True, bound), dst=self.rank + 1)
+        runner.restarts = 0
+        runner.special_rows = []
+
+    def begin(self, kw):
+        _arm_prune_end(self.eng, self.prune_end, self.runner.prune_blocks)
+        self.eng.streamBegin(self.part, **kw)
+        self.stream_open = True
+
+    # -- restart on the int32 kernels --------------------------------------------------------------------------
+    def may_restart(self, e):
+        """an overflow report of the packed kernels, once: not on the int32 kernels, which have no such range"""
+        return "EOVERFLOW16" in str(e) and not self.kw.get("force_int32") and self.runner.restarts == 0
+
+    def begin_on_int32(self):
+        """the packed kernel left its exact range: everything handed out so far is exact (the engine only
+        reports rows below the failing strip), so the band starts again on the int32 kernel and REPLAYS --
+        the inbound rows already received are still in the engine's column (pinned, or the port), outbound
+        segments already sent are not sent again (a port is simply written again with the same cells).
+        Called with the lock held and no stream open."""
+        kw = dict(self.kw, force_int32=True)
+        if self.host_fed:
+            kw["first_column_resume_rows"] = self.fed
+        self.begin(kw)
+        self.runner.restarts += 1
+
+    # -- inbound receiver (host transport) ---------------------------------------------------------------------
+    def receive(self):
+        """inbound boundary column: blocking recv of row segments from the left neighbour"""
+        runner, row0, inbound_h = self.runner, self.row0, self.inbound_h
+        try:
+            for q in range(self.nseg):
+                r0 = q * self.seg
+                ln = min(self.seg, self.m - r0)
+                buf = runner._tensor(ln)
+                self.dist.recv(buf, src=self.rank - 1)
+                if self.rx_stop.is_set():          # the run has ended (stop()): nothing more goes to the engine
+                    return
+                if self.digest_inbound:
+                    runner.inbound_crc = zlib.crc32(buf.numpy().tobytes(), runner.inbound_crc)
+                a0 = row0 + r0                     # the segment's first row in the whole band
+                if runner.inbound_column is not None:
+                    runner.inbound_column[a0 + 1:a0 + ln + 1] = buf.numpy()
+                if inbound_h is not None:          # H of the boundary column at every possible special row
+                    q0 = a0 // 256 + 1
+                    q1 = (a0 + ln) // 256
+                    if q1 >= q0:
+                        inbound_h[q0:q1 + 1] = buf.numpy()[q0 * 256 - 1 - a0:q1 * 256 - a0:256, 0]
+                with self.lock:
+                    self.eng.streamFeedColumn(r0, buf.numpy())
+                    self.fed = r0 + ln
+        except BaseException as e:     # surfaced by the main loop
+            self.errors.append(e)
+
+    # -- running-best exchange (host transport) ----------------------------------------------------------------
+    def exchange_best(self):
+        """the chain's running best travels between the rank processes (p2p: between the kernels); the thread keeps answering
+        the other bands until every band is through"""
+        import torch
+        runner, eng, dist, bx_stop = self.runner, self.eng, self.dist, self.bx_stop
+        known = -INF
+        try:
+            while True:
+                mine = eng.streamRunningBest() if not bx_stop.is_set() else -INF
+                t = torch.tensor([max(mine, known), -1 if bx_stop.is_set() else 0], dtype=torch.int64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=runner._best_group)
+                if int(t[0]) > known:
+                    known = int(t[0])
+                    if known > mine and not bx_stop.is_set():
+                        try:
+                            eng.streamBestHint(known)
+                            runner.hints += 1
+                        except AlignerError:
+                            pass
+                if int(t[1]) == -1:                  # every band is through
+                    return
+                time.sleep(0.002)
+        except BaseException as e:
+            self.errors.append(e)
+
+    def start_side_threads(self):
+        self.runner.hints = 0
+        if self.prune and self.world > 1 and not self.p2p and self.runner._best_group is not None:
+            self.bx = threading.Thread(target=self.exchange_best, daemon=True)
+            self.bx.start()
+        if self.host_fed:
+            self.rx = threading.Thread(target=self.receive, daemon=True)
+            self.rx.start()
+
+    # -- special-row hand-over ---------------------------------------------------------------------------------
+    def find_special_rows(self):
+        """special rows of this band: DP rows (multiples of the strip height, AbstractDiagonalAligner::isSpecialRow), as the
+        stream that has just begun places them.  After a restart on the int32 kernels (other strip heights) the rows
+        already handed over stay, the rest are where the new geometry puts them."""
+        if self.interval <= 0:
+            return
+        self.special_dp = []
+        while True:
+            try:
+                dp, _ = self.eng.streamReadSpecialRow(len(self.special_dp), 0, 0)
+            except (AlignerError, IndexError):
+                break
+            self.special_dp.append(int(dp))
+        done = self.runner.special_rows
+        self.special_next = sum(1 for dp in self.special_dp if done and self.row0 + dp <= done[-1])
+
+    def flush_special(self, rows_ok):
+        """hands over every special row whose strip is complete; called with the lock held"""
+        while self.special_next < len(self.special_dp) and self.special_dp[self.special_next] <= rows_ok:
+            k, dp = self.special_next, self.special_dp[self.special_next]
+            if self.host_fed and self.fed < dp:
+                return                                  # its boundary cell is still on the way
+            _, cells = self.eng.streamReadSpecialRow(k)
+            dpa = self.row0 + dp                        # the row in the whole band
+            if self.first:
+                h = _border_h(self.first_col_init_type, dpa)
+            elif self.p2p:
+                h = int(self.eng.portRead(dp - 1, 1)[0, 0])
+            else:
+                h = int(self.inbound_h[dpa // 256])
+            if self.sink is not None:
+                self.sink(dpa, np.array([h, -INF], dtype=np.int32), cells)
+            self.runner.special_rows.append(dpa)
+            self.special_next += 1
+
+    # -- the poll / send loop ----------------------------------------------------------------------------------
+    def send_segments(self, rows_done):
+        """outbound boundary column (host transport): every complete segment goes to the right neighbour"""
+        import torch
+        sent = False
+        while not self.last and not self.p2p and self.send_q < self.nseg:
+            r0 = self.send_q * self.seg
+            ln = min(self.seg, self.m - r0)
+            if rows_done < r0 + ln:
+                break
+            buf = self.runner._tensor(ln)
+            with self.lock:
+                buf.copy_(torch.from_numpy(self.eng.streamReadColumn(r0, ln)))
+            self.dist.send(buf, dst=self.rank + 1)
+            self.send_q += 1
+            sent = True
+        return sent
+
+    def fail(self):
+        """a side thread or the watchdog has given up: the stream is stopped and the first error raised"""
+        self.bx_stop.set()
+        with self.lock:
+            _stop_stream(self.eng, AlignerError, guard_abort=False)
+            self.stream_open = False
+        if self.bx is not None:           # (it leaves its loop at the next all_reduce in which every band has said stop)
+            self.bx.join(timeout=5.0)
+        raise self.errors[0]
+
+    def poll(self):
+        # a chain that stands still says where: one line per 10 s without progress on this band (rows completed,
+        # segments sent), one per second with MI355SW_BAND_DEBUG=1; after MI355SW_BAND_STALL_S seconds (default
+        # 900) without progress the band gives up instead of hanging its neighbours for ever
+        debug = os.environ.get("MI355SW_BAND_DEBUG") == "1"
+        stall_abort = self.runner.stall_abort_s if self.runner.stall_abort_s is not None else float(os.environ.get("MI355SW_BAND_STALL_S", "900"))
+        t_dbg = t_prog = time.time()
+        seen = (-1, -1)
+        rows_done, fin = 0, False
+        while True:
+            now = time.time()
+            if now - t_dbg >= (1.0 if debug else 10.0):
+                t_dbg = now
+                if (rows_done, self.send_q) != seen:
+                    seen, t_prog = (rows_done, self.send_q), now
+                if debug or now - t_prog >= 10.0:
+                    sys.stderr.write("[band %d/%d] rows_done=%d/%d finished=%d segments_sent=%d/%d no progress for %.0f s\n"
+                                     % (self.rank, self.world, rows_done, self.m, int(fin), self.send_q, self.nseg, now - t_prog))
+                    sys.stderr.flush()
+                if now - t_prog >= stall_abort:
+                    self.errors.append(RuntimeError("band %d/%d: no progress for %.0f s (rows_done=%d/%d, segments_sent=%d/%d)"
+                                                    % (self.rank, self.world, now - t_prog, rows_done, self.m, self.send_q, self.nseg)))
+            if self.errors:
+                self.fail()
+            with self.lock:
+                try:
+                    rows_done, fin = self.eng.streamPoll()
+                except AlignerError as e:
+                    if not self.may_restart(e):
+                        raise
+                    if os.environ.get("MI355SW_VERBOSE"):
+                        print("[bands] band %d/%d restarts on the int32 kernels: %s" % (self.rank, self.world, e), file=sys.stderr)
+                    _stop_stream(self.eng, AlignerError)
+                    self.begin_on_int32()
+                    self.find_special_rows()
+                    continue
+                # (device-resident rows are read through the copy stream: only once nothing more has to be fed, so that
+                #  a copy held up behind the running kernel cannot starve that kernel of its first column)
+                if self.special_dp and (not self.host_fed or self.fed >= self.m or fin):
+                    self.flush_special(rows_done)
+            sent = self.send_segments(rows_done)
+            if fin and (self.last or self.p2p or self.send_q >= self.nseg):
+                return
+            if not sent:
+                time.sleep(self.poll_sleep)
+
+    # -- finish ------------------------------------------------------------------------------------------------
+    def end_stream(self):
+        """the end of a stream that has computed every row: the edge best is read, `before_end` called, the stream ended.
+        Returns the band's best, or None where streamEnd reported an overflow that a run on the int32 kernels answers."""
+        if self.edges_here:
+            self.runner.edge_best = tuple(int(x) for x in self.eng.streamEdgeBest(self.edges_here))
+        if self.before_end is not None:       # e.g. read this band's slice of the last row while the stream is open
+            self.before_end(self.eng)
+        self.bx_stop.set()                   # the exchange thread keeps answering the other bands until every band is through
+        try:
+            return self.eng.streamEnd()[0]
+        except AlignerError as e:            # e.g. reported by the exact-position pass of a very tall band
+            if not self.may_restart(e):
+                raise
+            return None
+
+    def finish(self):
+        if self.rx is not None:
+            self.rx.join()
+        if self.special_dp:
+            with self.lock:
+                self.flush_special(self.m)
+        if self.digest_inbound and self.p2p and not self.first:
+            self.runner.inbound_crc = zlib.crc32(np.ascontiguousarray(self.eng.portRead(0, self.m), dtype=np.int32).tobytes())
+        if self.runner.inbound_column is not None and self.p2p:
+            self.runner.inbound_column[1:] = self.eng.portRead(0, self.m)
+        best = self.end_stream()
+        if best is None:
+            with self.lock:              # (the stream is over and every special row handed over: nothing to stop, nothing to probe)
+                self.begin_on_int32()
+            while not self.eng.streamPoll()[1]:          # (rows done, finished)
+                time.sleep(self.poll_sleep)
+            best = self.end_stream()
+        self.stream_open = False
+        if self.bx is not None:
+            self.bx.join()
+        if self.errors:
+            raise self.errors[0]
+        return best
+
+    def stop(self):
+        self.rx_stop.set()
+        self.bx_stop.set()
+        if self.rx is not None:            # (a receiver in the middle of a feed finishes it before the stream goes)
+            self.rx.join(timeout=5.0)
+        if self.stream_open:
+            self.stream_open = False
+            _stop_stream(self.eng, Exception)
 
 
 class InProcessChain:
@@ -731,7 +803,6 @@ class InProcessChain:
         best cell of that edge (BandRunner.run); the int32 retry after an overflow computes every cell.
         initial_bound: a caller's first bound of a pruning chain -- the score of an admissible alignment that exists; the
         larger of it and the seed's is what every band starts from, and what the result is held to (check_chain_bound)."""
-        from .engine import AlignerError
         als, N = self.aligners, len(self.aligners)
         n = limits[-1]
         sw = recurrence == SMITH_WATERMAN
@@ -739,33 +810,21 @@ class InProcessChain:
         self.attach(m)
         self.initial_bound = None
         if self.prune_blocks and self.seed_bound and N > 1:
-            if prune_end:
-                self.initial_bound = edge_seed_bound(als[0], m, n, first_row_init_type, first_col_init_type)
-            else:
-                self.initial_bound = chain_seed_bound(als[0], m, n, recurrence, first_row_init_type, first_col_init_type)
+            self.initial_bound = _seed_bound(als[0], m, n, recurrence, prune_end, first_row_init_type, first_col_init_type)
         if self.prune_blocks and initial_bound is not None:
             self.initial_bound = int(initial_bound) if self.initial_bound is None else max(self.initial_bound, int(initial_bound))
         for attempt in (0, 1):
             begun = []
             try:
                 for k in range(N):                         # left to right: band k+1's kernel starts after band k's
-                    kw = dict(recurrence_type=recurrence, track_best=sw, first_row_init_type=first_row_init_type,
-                              first_row_start_offset=limits[k], last_column_port=k < N - 1,
-                              want_last_row=(not sw and k == N - 1) or bool(prune_end & 1),
-                              want_last_column=bool(prune_end & 2) and k == N - 1, force_int32=bool(force_int32 or attempt))
-                    if self.prune_blocks:
-                        kw.update(prune_blocks=True, prune_rows=m, prune_cols=n - limits[k], share_best=N > 1)
-                        if self.initial_bound is not None:
-                            kw.update(initial_bound=self.initial_bound)
-                    if k == 0:
-                        kw.update(first_column_init_type=first_col_init_type)
-                    else:
-                        corner = np.array([[0, -INF]], dtype=np.int32)
-                        if first_row_init_type != INIT_WITH_ZEROES:
-                            corner[0, 0] = -2 * limits[k] - (3 if first_row_init_type == 1 else 0)
-                        kw.update(first_column_init_type=INIT_WITH_CUSTOM_DATA, first_column=corner, first_column_port=True)
-                    if prune_end and self.prune_blocks:
-                        als[k].setPruneEnd(prune_end)      # (the int32 retry too: the engine then drops it together with the pruning)
+                    last = k == N - 1
+                    # (every column travels through a port; a global run that ends in the last cell reads it from the last row)
+                    kw = _stream_keywords(m, limits[k], n, k == 0, last, True, N > 1, recurrence, sw, first_row_init_type,
+                                          first_col_init_type, prune_end, self.prune_blocks, not sw and last,
+                                          bool(force_int32 or attempt))
+                    if self.prune_blocks and self.initial_bound is not None:
+                        kw.update(initial_bound=self.initial_bound)
+                    _arm_prune_end(als[k], prune_end, self.prune_blocks)
                     als[k].streamBegin(Partition(0, limits[k], m, limits[k + 1]), **kw)
                     begun.append(k)
                 open_ = set(range(N))
@@ -779,7 +838,7 @@ class InProcessChain:
                 bests, stats, h_last = [], [], None
                 for k in range(N):
                     if prune_end:
-                        here = (prune_end & 1) | ((prune_end & 2) if k == N - 1 else 0)
+                        here = _edges_held(prune_end, k == N - 1)
                         edge = als[k].streamEdgeBest(here) if here else (-1, -1, -INF)
                     elif not sw and k == N - 1:
                         h_last = int(als[k].streamReadLastRow(col=limits[k + 1] - limits[k] - 1, length=1)[0, 0])
@@ -794,15 +853,18 @@ class InProcessChain:
                 return best, stats
             except AlignerError as e:
                 for k in begun:                            # stop whatever is running, then the whole chain again on the int32 kernels
-                    for fn in (als[k].streamAbort, als[k].streamEnd):
-                        try:
-                            fn()
-                        except AlignerError:
-                            pass
+                    _stop_stream(als[k], AlignerError)
                 if "EOVERFLOW16" not in str(e) or force_int32 or attempt == 1:
                     raise
                 self.restarts += 1
                 self.attach(m)
+
+
+def _special_row_spacing(m, n, sra_limit, extent=None):
+    """rows between two special rows of a band's area of `sra_limit` bytes (0: none are kept).  The spacing follows the sizes of
+    the whole, untrimmed matrix (Job.cpp:62-67): `extent`, or m x n"""
+    em, en = extent if extent is not None else (m, n)
+    return sra_mod.flush_interval(em, en, sra_limit) if sra_limit > 0 else 0
 
 
 def _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_row_init_type, first_col_init_type, origin, run_kw,
@@ -812,13 +874,10 @@ def _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_r
     (the band's own best as the engine reports it -- for a global run that ends in the last cell, prune_end 0 and nothing
     tracked, the last band's (m-1, j1-1, H[m][j1]) and nothing for the others --, the partition, the DP rows written).
     origin = (i, j): the cell of the whole matrix the chain's (0, 0) is (a --trim: the files keep absolute coordinates)."""
-    from . import sra as sra_mod
     first, last = runner.rank == 0, runner.rank == runner.world - 1
     oi, oj = origin
     os.makedirs(bwork, exist_ok=True)
-    # (the spacing follows the sizes of the whole, untrimmed matrix: Job.cpp:62-67)
-    em, en = extent if extent is not None else (m, n_total if n_total is not None else j1)
-    interval = sra_mod.flush_interval(em, en, sra_limit) if sra_limit > 0 else 0
+    interval = _special_row_spacing(m, n_total if n_total is not None else j1, sra_limit, extent)
     area = sra_mod.SpecialRowsArea(sra_mod.special_rows_path(bwork, 1, 0), disk_limit=max(sra_limit, 1))
     part = area.create_partition(oi, oj + j0, oi + m, oj + j1)
     part.set_border_markers(first_row_init_type, j0, first_col_init_type if first else INIT_WITH_CUSTOM_DATA, 0)
@@ -845,7 +904,7 @@ def _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_r
                            special_row_sink=sink if interval > 0 else None, n_total=n_total, want_last_row=True,
                            before_end=before_end, keep_inbound=not first, **run_kw)
     if first:
-        lead = 0 if first_col_init_type == INIT_WITH_ZEROES else -2 * m - (3 if first_col_init_type == 1 else 0)
+        lead = _border_h(first_col_init_type, m)
     else:
         lead = int(runner.inbound_column[m, 0])
         runner.inbound_column.tofile(os.path.join(part.path, "C00000000.INIT_WITH_CUSTOM_DATA"))
@@ -860,7 +919,6 @@ def _band_area(runner, m, j0, j1, bwork, sra_limit, n_total, recurrence, first_r
 
 def _write_chain_best(bwork, best, origin=(0, 0)):
     """`crosspoints/crosspoint_01.00` of a band: the chain's best, the engine's 0-based cell as DP coordinates of the whole matrix"""
-    from . import sra as sra_mod
     if best[0] >= 0 or best[1] >= 0:
         best = (best[0] + 1 + origin[0], best[1] + 1 + origin[1], best[2])
         sra_mod.write_crosspoint(sra_mod.crosspoint_path(bwork, 1, 0), best)
@@ -944,7 +1002,6 @@ CHAIN_STATE, CHAIN_COLUMN, CHAIN_STATE_VERSION = "chain.mi355", "last_column.mi3
 
 
 def _save_chain_state(bwork, state):
-    import json
     fn = os.path.join(bwork, CHAIN_STATE)
     with open(fn + ".tmp", "w") as f:
         json.dump(state, f, sort_keys=True)
@@ -964,7 +1021,6 @@ def _rows_on_disk(bwork):
 
 def _load_chain_state(bwork, key, band):
     """the state a band left, checked against this call: None when the band's directory holds nothing to continue"""
-    import json
     fn = os.path.join(bwork, CHAIN_STATE)
     if not os.path.exists(fn):
         if _rows_on_disk(bwork):
@@ -996,12 +1052,34 @@ def _inbound_file(works, k, m):
     return None
 
 
-def _corner_cell(first_row_init_type, j):
-    """(H, E) of DP cell (0, j) on the first row: the corner of the band that starts at column j (BandRunner.run)"""
-    h = 0
-    if first_row_init_type != INIT_WITH_ZEROES and j > 0:
-        h = -2 * j - (3 if first_row_init_type == 1 else 0)
-    return np.array([[h, -INF]], dtype=np.int32)
+def _left_by_earlier_runs(works, m, limits, n_total, sra_limit, origin, extent, recurrence, first_row_init_type,
+                          first_col_init_type, prune_blocks, prune_end, track_best):
+    """serial_band_stage1(resume=True): what the bands left in `works`, checked before anything runs.  Returns (the key of this
+    run, the state of every band or None, the first band that has to run)."""
+    N = len(works)
+    key = {"m": int(m), "limits": [int(x) for x in limits], "origin": [int(x) for x in origin],
+           "extent": [int(x) for x in extent] if extent is not None else None, "n_total": int(n_total),
+           "recurrence": int(recurrence), "first_row_init_type": int(first_row_init_type),
+           "first_col_init_type": int(first_col_init_type), "track_best": bool(track_best),
+           "prune_end": int(prune_end), "prune_blocks": bool(prune_blocks), "sra_limit": int(sra_limit),
+           "special_row_interval": int(_special_row_spacing(m, n_total, sra_limit, extent))}
+    states = [_load_chain_state(works[k], key, k) for k in range(N)]
+    for bwork in works:                               # leftovers of a killed run
+        for d, _dirs, files in os.walk(bwork):
+            for f in files:
+                if f.endswith(".tmp"):
+                    os.remove(os.path.join(d, f))
+    # bands that are done -- the state says so and the completion marker, the last row, is on disk -- are not run again;
+    # the first band that is not needs the column of the band on its left, whole
+    k_first = 0
+    while k_first < N and states[k_first] is not None and states[k_first].get("done") and m in _rows_on_disk(works[k_first]):
+        k_first += 1
+    while 0 < k_first < N:
+        if _inbound_file(works, k_first, m) is not None:
+            break
+        k_first -= 1                                  # (no column to start from: the band on the left runs again, from row 0)
+        states[k_first] = dict(states[k_first], done=False, rows=[], column_rows=0)
+    return key, states, k_first
 
 
 def _kernel_prunes(name):
@@ -1088,7 +1166,6 @@ class _BandResume:
             self.state["initial_bound"] = int(self.runner.initial_bound)
 
     def special_row(self, dp):
-        from . import sra as sra_mod
         sra_mod.drain()                  # the row's file is in place (written, renamed) before the state names it
         self._bound_seen()
         self.state["rows"].append(int(dp))
@@ -1116,7 +1193,6 @@ class _BandResume:
             self.link.on_segment = None
 
     def finish(self, record):
-        from . import sra as sra_mod
         sra_mod.drain()
         self.close()
         self.state = dict({"version": CHAIN_STATE_VERSION, "key": self.key, "band": self.band, "done": True}, **record)
@@ -1171,32 +1247,11 @@ def serial_band_stage1(engine, m, limits, work, sra_limit, n_total=None, recurre
     link = _SerialLink() if N > 1 else None
     prune_end = run_kw.get("prune_end", 0)
     works = [os.path.join(work, "FORK.%02d" % k) if N > 1 else work for k in range(N)]
-    # ---- resume: what the bands left, checked before anything runs ----
     key, states, k_first = None, [None] * N, 0
     if resume:
-        from . import sra as sra_mod
-        em, en = extent if extent is not None else (m, n_total)
-        key = {"m": int(m), "limits": [int(x) for x in limits], "origin": [int(x) for x in origin],
-               "extent": [int(x) for x in extent] if extent is not None else None, "n_total": int(n_total),
-               "recurrence": int(recurrence), "first_row_init_type": int(first_row_init_type),
-               "first_col_init_type": int(first_col_init_type), "track_best": bool(run_kw.get("track_best", True)),
-               "prune_end": int(prune_end), "prune_blocks": bool(prune_blocks), "sra_limit": int(sra_limit),
-               "special_row_interval": int(sra_mod.flush_interval(em, en, sra_limit)) if sra_limit > 0 else 0}
-        states = [_load_chain_state(works[k], key, k) for k in range(N)]
-        for bwork in works:                               # leftovers of a killed run
-            for d, _dirs, files in os.walk(bwork):
-                for f in files:
-                    if f.endswith(".tmp"):
-                        os.remove(os.path.join(d, f))
-        # bands that are done -- the state says so and the completion marker, the last row, is on disk -- are not run again;
-        # the first band that is not needs the column of the band on its left, whole
-        while k_first < N and states[k_first] is not None and states[k_first].get("done") and m in _rows_on_disk(works[k_first]):
-            k_first += 1
-        while 0 < k_first < N:
-            if _inbound_file(works, k_first, m) is not None:
-                break
-            k_first -= 1                                  # (no column to start from: the band on the left runs again, from row 0)
-            states[k_first] = dict(states[k_first], done=False, rows=[], column_rows=0)
+        key, states, k_first = _left_by_earlier_runs(works, m, limits, n_total, sra_limit, origin, extent, recurrence,
+                                                     first_row_init_type, first_col_init_type, prune_blocks, prune_end,
+                                                     run_kw.get("track_best", True))
     midband = not run_kw.get("track_best", True)          # a chain that tracks a best cell restarts its band at row 0
     resumed = None
     if resume and any(s is not None for s in states):
