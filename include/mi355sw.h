@@ -165,8 +165,8 @@ typedef struct {
                                                reproducible pruning (MI355SW_F_DETERMINISTIC_PRUNE is ignored by this
                                                family), the partitions of mi355sw_align_partitions, and the diagonal seed -- it needs the packed
                                                kernels, so a caller hands a bound in through initial_bound (mi355sw_seed_bound makes one where the
-                                               pair runs on the packed kernels).  No pruning window, fast-forward or retire: every strip walks the
-                                               whole width. */
+                                               pair runs on the packed kernels).  By itself every strip walks the whole width and writes every
+                                               skipped cell; the pruning window of this family is MI355SW_F_INT32_WINDOW. */
 #define MI355SW_F_INT32_PRUNE_EDGE_GOAL 262144 /* the EDGE rule (mi355sw_set_prune_end) and GOAL bounds (mi355sw_set_goal_bounds) on the int32 kernel family too
                                                (additive in ABI 8; off by default: without it every run is what it was, such a request on the int32
                                                kernels computes every cell).  A flag of its own: MI355SW_F_INT32_PRUNE_GLOBAL alone serves neither, and
@@ -189,7 +189,30 @@ typedef struct {
                                                The unit is one 64-step slab of a strip, skipped cells read H = E = F = -INF, pruned_cells +
                                                processed_cells = m * n.  NOT served, every cell computed as before: MI355SW_F_DETERMINISTIC_PRUNE (with
                                                it this family drops both requests; a saved pruning state stays refused), block_score_columns > 0, a
-                                               local recurrence, a tracking manager.  No pruning window, fast-forward or retire. */
+                                               local recurrence, a tracking manager.  The pruning window of this family: MI355SW_F_INT32_WINDOW. */
+#define MI355SW_F_INT32_WINDOW 524288       /* the pruning WINDOW on the int32 kernel family (additive in ABI 8; off by default: without it every run is
+                                               what it was, every strip of a pruning int32 run walks the whole width and writes every skipped cell).
+                                               With it, wherever that family already prunes -- the local rule, the last-cell rule under
+                                               MI355SW_F_INT32_PRUNE_GLOBAL, the edge rule and goal bounds under MI355SW_F_INT32_PRUNE_EDGE_GOAL; 15 or
+                                               more common byte values (63 or more with MI355SW_F_WIDE_ALPHABET), MI355SW_F_FORCE_INT32, the rerun after
+                                               an MI355SW_EOVERFLOW16 report (the rerun keeps the flag) -- the windowed twin of the kernel runs
+                                               (mi355sw_stats.kernel: all eight template arguments, sw_strip_kernel<R,..,true,GOAL,EDGE,true>):
+                                               * a strip's last progress word says from which column on its row is the skip constant, and the strip
+                                                 below takes the constant for those cells whatever the memory holds;
+                                               * the trailing chunks of a strip go through the slab test too, so a skipped state survives to the end
+                                                 of a row;
+                                               * a strip whose state is the skip state behind that column, and whose rule lets the slab in front of it
+                                                 go, RETIRES: it leaves the row unwalked and unwritten (the strips below the end of the alignment end
+                                                 after three chunks), its slabs count as pruned (pruned_cells + processed_cells = m * n as before);
+                                               * a strip that cannot retire FAST-FORWARDS: behind a skipped slab, up to 16 slabs the strip above has
+                                                 already published are tested in one go and the leading run that can go is written out with one
+                                                 progress flag -- the same decisions, cells and counts as slab by slab.
+                                               Special rows and the last row start out as the constant -- (0, -INF) local, (-INF, -INF) global -- so
+                                               every row handed out holds the pruned criterion exactly as without the flag: which slabs go is decided
+                                               by the same tests, only what is written changes.  A band of a chain is windowed on its own.
+                                               MI355SW_F_NO_WINDOW switches it off, as for the packed family.  NOT served, the walk stays as it is:
+                                               block_score_columns > 0 (block scores), MI355SW_F_DETERMINISTIC_PRUNE, the partitions of a batch's shared
+                                               launch.  No gap words and no jump (this family has no band mode), and no mid-strip stop. */
 #define MI355SW_F_NO_HOST_COUNTER 512       /* the kernel does not mirror its strip counter into host memory (measurements) */
 #define MI355SW_V_MESSAGES 1                /* one line per noteworthy event (overflow reruns, the diagonal seed, ...) */
 #define MI355SW_V_JOBS 2                    /* timing of every mi355sw_align_partition job */

@@ -10,6 +10,10 @@ namespace mi355sw {
 
 enum { CHUNK = 64 };   // bus columns staged per hand-off (one per lane)
 enum { DET_UNSET = (int) 0x80000000 };   // KernelArgs::det_prefix entry that has not been written yet
+// The pruning window, both kernel families: a strip's LAST progress word is WIN_RETIRED + X -- "done, and from output column X on
+// everything I left is the skip constant, written or not" (sw_kernel_pk16.inc, "the pruning WINDOW"; sw_kernel.hip, WINDOW).
+// Every wait compares `progress >= columns needed`, which the large value satisfies; arithmetic strips the flag first.
+#define WIN_RETIRED 0x40000000
 
 // M/libmasa/IManager.hpp:36-47
 enum { INIT_WITH_ZEROES = 0, INIT_WITH_GAPS = 1, INIT_WITH_CUSTOM_DATA = 2, INIT_WITH_GAPS_OPENED = 3 };
@@ -301,7 +305,7 @@ hipError_t launch_batch_kernel_pk16_goal(const BatchArgs* dbatch, int rows_per_h
 
 // `dargs` = device copy of the argument block (the launcher uploads `a` into it on `stream`)
 hipError_t launch_strip_kernel(const KernelArgs& a, KernelArgs* dargs, int rows_per_lane, int grid, hipStream_t stream,
-                               bool sw, bool profile, bool track);
+                               bool sw, bool profile, bool track, bool window = false);   // window: the windowed twin of a pruning instantiation
 int strip_kernel_waves_per_simd(int rows_per_lane);   // int32 family: wavefronts of one launch that share a SIMD (2 for 256/512-row strips; the packed kernels: 1)
 // packed 16-bit SW kernel (sw_kernel_pk16.inc, instantiated by sw_kernel_pk16_{a..j}.hip): strip height = 128*rows_per_half
 hipError_t launch_strip_kernel_pk16(const KernelArgs& a, KernelArgs* dargs, int rows_per_half, int grid, hipStream_t stream, bool track, bool sw);

@@ -171,8 +171,9 @@ __device__ __forceinline__ void wave_step(LaneState<R>& st, WaveLds* lds, const 
 // PRUNE (round 5; local alignments): block pruning in the int32 family too -- the reference prunes in every instantiation of
 // its kernels (X/CUDAligner.cu:950-960); here a 64-step slab of the strip is skipped when nothing that enters it (the lanes'
 // chunk maxima, the bus cells above it) can still reach the running best, exactly the packed kernel's local test
-// (sw_kernel_pk16.inc, SW_PRUNE_MARGIN included).  Skipped cells read H = 0, E = F = -INF.  No window, no fast-forward: this
-// family takes the pairs the packed kernel cannot (more than 14 common byte values) and its reruns.
+// (sw_kernel_pk16.inc, SW_PRUNE_MARGIN included).  Skipped cells read H = 0, E = F = -INF.  This family takes the pairs the
+// packed kernel cannot (more than 14 common byte values) and its reruns.  By itself a strip walks the whole width slab by slab;
+// window, retire and fast-forward are the WINDOW instantiations' (opt-in, MI355SW_F_INT32_WINDOW: see process_strip).
 #define SW32_PRUNE_MARGIN 8
 // PRUNE && !SW (global alignments; opt-in, MI355SW_F_INT32_PRUNE_GLOBAL): the packed family's last-cell rule (DESIGN.md
 // section 4, "Global"; AbstractBlockPruning.cpp:92-109) on int32 values, slab by slab.  gbest holds a running LOWER bound of
@@ -242,11 +243,53 @@ __device__ __forceinline__ void clamp_void32(LaneState<R>& st) {
     st.tbot = max(st.tbot, NEG_INF - GAP_FIRST);
     st.fbot = max(st.fbot, NEG_INF);
 }
-template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false, bool GOAL = false, bool EDGE = false>
+// WINDOW (opt-in, MI355SW_F_INT32_WINDOW; every pruning instantiation has a windowed twin): the packed family's pruning window
+// (sw_kernel_pk16.inc, "the pruning WINDOW") without gap words -- this family has no band mode, so nothing ever jumps.
+//   a. the predecessor's last progress word is WIN_RETIRED + X (sw_kernel.h): from output column X on its row is the skip
+//      constant, written or not, and the chunk head substitutes the constant for whatever bus[col >= X] holds;
+//   b. the trailing chunks of a non-ragged strip (col0 + CHUNK > n) go through the slab test too, with the same entries: bus
+//      cells at col >= n enter nothing, and a lane that has passed column n - 1 (jl >= n) is no entry and keeps its state --
+//      tl / e are its final last-column cells, which the epilogue hands out;
+//   c. void_from is the first output column from which everything the strip has left is the constant (a computed chunk resets
+//      it).  The strip RETIRES at a chunk whose test says skip when the slab before was skipped (its state is the skip state) and
+//      the predecessor's X <= col0 (nothing but the constant enters from above, for good): the local test is monotone in the
+//      column and gbest only grows, a global strip in that state holds nothing and nothing enters.  It leaves the chunk loop,
+//      counts the slabs it did not walk as pruned, writes its last column from its state and publishes WIN_RETIRED + void_from.
+//      A strip that walks to the end publishes WIN_RETIRED + min(void_from, n) with its last chunk; a ragged strip never retires.
+//   d. FAST-FORWARD: after a skipped slab the strip's state is a constant, so the test of the slabs that follow depends on the bus
+//      cells above them alone (after substitution a).  From chunk 3 on, up to SW32_FF full slabs the predecessor has ALREADY
+//      published (one look at its word, no wait) are fetched and tested in one go, with gseen as it stood at the first; the
+//      leading run that can go is written out together -- the bus cells, with the emit lag; special rows and the last row hold the
+//      constant already -- with one drain and one progress flag, pruned_slabs rises by the run, and the seq1 codes of the last
+//      slab of the run are staged for the chunk that follows.  Decisions, cells and counts are those of slab by slab.
+// No new wait: the poll is the existing one with its spin_limit, and a retired predecessor's word satisfies it.  Rows that leave
+// the device (special rows, the last row) are pre-filled with the constant by the host (mi355sw_stream_begin).
+// WINDOW is the last parameter and defaults to false: every instantiation named without it is the kernel it was under
+//   template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false, bool GOAL = false, bool EDGE = false>
+// (every `if (WINDOW)` below folds away; the parent's register, scratch and instruction counts per kernel are kept: CHANGELOG.md).
+#define SW32_FF 16     // slabs per fast-forward batch
+#define SW32_FFB 4     // ... fetched SW32_FFB at a time
+// the slab test of a strip in the skip state (fast-forward): what enters is the bus cell above alone -- `top_h` its H, column `col`
+// of the slab that starts at `col0`; the lane itself holds the constant (local: t = -GAP_FIRST) or nothing (global)
+template <bool SW, bool GOAL, bool EDGE>
+__device__ __forceinline__ bool void_slab_goes32(const int top_h, const int col0, const int col, const int pr_rows, const int pr_cols, const int gseen,
+                                                 const int prune_end, const long long gcol, const long long grow, const bool goal_any) {
+    if (SW) {
+        const int left = min(pr_rows + 2, pr_cols + 1 - (col0 - CHUNK));
+        const int e = max(-GAP_FIRST, top_h - GAP_FIRST);
+        return !__any(e + left + SW32_PRUNE_MARGIN >= gseen);
+    }
+    if (GOAL) return goal_any && !__any(goal_keep32(top_h - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, gcol, grow));
+    const int top = EDGE ? edge_upper32(prune_end, top_h - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, 1)
+                         : nw_upper32(top_h - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, 1);
+    return !__any(top >= gseen);
+}
+template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false, bool GOAL = false, bool EDGE = false, bool WINDOW = false>
 __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, const int s_in, WaveLds* lds, const int lane) {
     constexpr bool NWP = PRUNE && !SW;                  // the global (last-cell) rule, and its two variants:
     static_assert(!GOAL || (PRUNE && !SW && !TRACK), "goal mode: global recurrence, pruning kernels, nothing tracked");
     static_assert(!EDGE || (PRUNE && !SW && !TRACK && !GOAL), "edge mode: global recurrence, pruning kernels, nothing tracked, no goal");
+    static_assert(!WINDOW || PRUNE, "the window: pruning kernels only");
     const UniformArgs a = uniform_args(ap);
     const int s = __builtin_amdgcn_readfirstlane(s_in);
     const int n = a->n;
@@ -325,6 +368,10 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
     const long long grow = goal_r <= NEG_INF / 2 ? 0x7fffffffffffffffll : (long long) goal_r;
     const bool goal_any = goal_c > NEG_INF / 2 || goal_r > NEG_INF / 2;
     const int prune_end = EDGE ? a->prune_end : 0;
+    // the window: the predecessor's X once its last word has been seen, this strip's own void_from, whether the slab before went
+    int pred_x = 0x7fffffff, void_from = 0x7fffffff;
+    bool prev_skip = false, retired = false;
+    int ff_block = -1;                 // the chunk a fast-forward ended in front of: it takes the ordinary path
 
     DBG(1, 1);
     // ---- sweep the strip ----
@@ -332,12 +379,66 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
         const int col0 = c * CHUNK;
         bool skip = false;
         DBG(2, c); DBG(3, 10);
+        // (0) window, fast-forward: the state is the skip state -- a run of slabs the strip above has already published goes in one step
+        if (WINDOW && prev_skip && !ragged && c >= 3 && c != ff_block && pred_x > col0) {
+            const int pv = poll_agent(prog_in);
+            if (pv >= WIN_RETIRED) pred_x = pv - WIN_RETIRED;
+            const int avail = min(pv >= WIN_RETIRED ? n : pv, n);
+            const int K = min((avail - col0) / CHUNK, (int) SW32_FF);       // full slabs ready above
+            if (K >= 2) {
+                if (!GOAL) gseen = max(gseen, poll_agent(a->gbest_in));
+                int run = 0;
+                // (SW32_FFB loads in flight at a time: the registers of R = 4 / 8 leave room for no more next to a strip's state)
+#pragma unroll 1
+                for (int g = 0; g < K && run == g; g += SW32_FFB) {
+                    int tops[SW32_FFB];
+#pragma unroll
+                    for (int k = 0; k < SW32_FFB; k++) {
+                        tops[k] = 0;
+                        if (g + k < K) tops[k] = ld_agent((const int*) &a->bus[col0 + (g + k) * CHUNK + lane]);
+                    }
+#pragma unroll
+                    for (int k = 0; k < SW32_FFB; k++) {
+                        if (g + k == run && g + k < K) {
+                            const int colk = col0 + (g + k) * CHUNK + lane;
+                            const int top_h = colk >= pred_x ? (NWP ? NEG_INF : 0) : tops[k];
+                            if (void_slab_goes32<SW, GOAL, EDGE>(top_h, col0 + (g + k) * CHUNK, colk, pr_rows, pr_cols, gseen, prune_end, gcol, grow, goal_any)) run = g + k + 1;
+                        }
+                    }
+                }
+                run = __builtin_amdgcn_readfirstlane(run);
+                if (run > 0) {
+                    const int2 cell = NWP ? make_int2(NEG_INF, NEG_INF) : make_int2(0, NEG_INF);
+#pragma unroll 1
+                    for (int k = 0; k < run; k++) st_agent2(&a->bus[col0 + k * CHUNK - 63 + lane], cell);
+                    const int last0 = col0 + (run - 1) * CHUNK;
+                    lds->c1[CHUNK + lane] = a->seq1[last0 + lane];      // what the next chunk shifts down as "the chunk before"
+                    pruned_slabs += run;
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (drain, then flag: as below)
+                    if (lane == 0) st_agent(prog_out, last0 + 1);
+                    c += run - 1;
+                    ff_block = c + 1;
+                    continue;
+                }
+            }
+            ff_block = c;
+        }
         // (1) input chunk: wait for the strip above, then stage bus + seq1 codes into LDS
         {
             int need = col0 + CHUNK;
             if (need > n) need = n;
             if (col0 < n) {
                 int spins = 0;
+                if (WINDOW) {
+                    // (the same wait; the word it ends on says whether the strip above is done, and from where its row is void)
+                    int pv = poll_agent(prog_in);
+                    while (pv < need && spins < spin_limit) {
+                        __builtin_amdgcn_s_sleep(2);
+                        spins++;
+                        pv = poll_agent(prog_in);
+                    }
+                    if (pv >= WIN_RETIRED) pred_x = pv - WIN_RETIRED;
+                } else
                 while (poll_agent(prog_in) < need && spins < spin_limit) {
                     __builtin_amdgcn_s_sleep(2);
                     spins++;
@@ -351,38 +452,45 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
                 hf = ld_agent2(&a->bus[col]);
                 code = a->seq1[col];
             }
+            // window: what the strip above left from its X on is the skip constant, whatever the memory holds; a lane that has
+            // passed the last column and a bus cell behind it enter no slab
+            if (WINDOW && col >= pred_x) hf = NWP ? make_int2(NEG_INF, NEG_INF) : make_int2(0, NEG_INF);
+            const bool passed = WINDOW && col0 - lane >= n, beyond = WINDOW && col >= n;
             if (PRUNE) {
                 if (!GOAL) gseen = max(gseen, poll_agent(a->gbest_in));     // (goal mode: the bounds are fixed, nothing is read)
                 if (GOAL) {
-                    if (!ragged && col0 >= 2 * CHUNK && col0 + CHUNK <= n) {
+                    if (!ragged && col0 >= 2 * CHUNK && (WINDOW || col0 + CHUNK <= n)) {
                         // (the same two entries as below, held against the sweep's own bounds: see goal_keep32)
-                        const bool own = goal_keep32(lane_entry, pr_rows - lane * R, pr_cols - col0 + lane + 2, R - 1, gcol, grow);
-                        const bool top = goal_keep32(hf.x - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, gcol, grow);
+                        const bool own = !passed && goal_keep32(lane_entry, pr_rows - lane * R, pr_cols - col0 + lane + 2, R - 1, gcol, grow);
+                        const bool top = !beyond && goal_keep32(hf.x - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, gcol, grow);
                         skip = goal_any && !__any(own || top);
                     }
                 } else if (EDGE) {
-                    if (!ragged && col0 >= 2 * CHUNK && col0 + CHUNK <= n) {
+                    if (!ragged && col0 >= 2 * CHUNK && (WINDOW || col0 + CHUNK <= n)) {
                         // (the same two entries and spans as below: see edge_upper32)
-                        const int own = edge_upper32(prune_end, lane_entry, pr_rows - lane * R, pr_cols - col0 + lane + 2, R - 1, 2);
-                        const int top = edge_upper32(prune_end, hf.x - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, 1);
+                        const int own = passed ? NEG_INF - 1 : edge_upper32(prune_end, lane_entry, pr_rows - lane * R, pr_cols - col0 + lane + 2, R - 1, 2);
+                        const int top = beyond ? NEG_INF - 1 : edge_upper32(prune_end, hf.x - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, 1);
                         skip = !__any(max(own, top) >= gseen);
                     }
                 } else if (NWP) {
-                    if (!ragged && col0 >= 2 * CHUNK && col0 + CHUNK <= n) {
+                    if (!ragged && col0 >= 2 * CHUNK && (WINDOW || col0 + CHUNK <= n)) {
                         // what enters the slab: the lane's own last column (its R rows, column col0 - lane - 1, one column
                         // of room on either side) and the bus cell of its column (the row above the strip; its left
                         // neighbour is the slab's corner)
-                        const int own = nw_upper32(lane_entry, pr_rows - lane * R, pr_cols - col0 + lane + 2, R - 1, 2);
-                        const int top = nw_upper32(hf.x - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, 1);
+                        const int own = passed ? NEG_INF - 1 : nw_upper32(lane_entry, pr_rows - lane * R, pr_cols - col0 + lane + 2, R - 1, 2);
+                        const int top = beyond ? NEG_INF - 1 : nw_upper32(hf.x - GAP_FIRST, pr_rows + 1, pr_cols - col + 1, 0, 1);
                         skip = !__any(max(own, top) >= gseen);
                     }
                 } else
-                if (!ragged && col0 >= 2 * CHUNK && col0 + CHUNK <= n) {
+                if (!ragged && col0 >= 2 * CHUNK && (WINDOW || col0 + CHUNK <= n)) {
                     // (lane k is k columns behind lane 0: the slab touches columns col0 - 63 .. col0 + 63)
                     const int left = min(pr_rows + 2, pr_cols + 1 - (col0 - CHUNK));
-                    const int e = max(lane_entry, hf.x - GAP_FIRST);
+                    const int e = max(passed ? NEG_INF : lane_entry, beyond ? NEG_INF : hf.x - GAP_FIRST);
                     skip = !__any(e + left + SW32_PRUNE_MARGIN >= gseen);
                 }
+                // retire: the state is the skip state, nothing but the constant enters from above from here on, and the rule
+                // lets this slab go -- as it will every slab to the right (see WINDOW above)
+                if (WINDOW && skip && prev_skip && pred_x <= col0) { retired = true; pruned_slabs += nchunks - c; break; }
             }
             // shift the seq1 window: [64,128) -> [0,64), then the new chunk
             const unsigned char prev = lds->c1[CHUNK + lane];
@@ -404,12 +512,18 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
             // the slab is not computed: every cell in it counts as H = 0 (t = -5), E = F = -INF
             // (global rule: H = -INF as well, and the lane then holds nothing -- cm stays at -INF)
             const int t_skip = NWP ? NEG_INF - GAP_FIRST : -GAP_FIRST;
+            // (window, trailing chunks: a lane that has passed column n - 1 holds its final last-column cells -- they stay)
+            const bool keep = WINDOW && jl >= n;
 #pragma unroll
-            for (int r = 0; r < R; r++) { st.tl[r] = t_skip; st.e[r] = NEG_INF; }
+            for (int r = 0; r < R; r++) { st.tl[r] = keep ? st.tl[r] : t_skip; st.e[r] = keep ? st.e[r] : NEG_INF; }
             st.tup_prev = t_skip; st.tbot = t_skip; st.fbot = NEG_INF;
             lds->out_tf[lane] = make_int2(t_skip, NEG_INF);
             if (!NWP) cm = -GAP_FIRST;
             pruned_slabs++;
+            if (WINDOW) {
+                if (!prev_skip) void_from = max(0, col0 - 63);      // (the emit lag: this slab's output columns start there)
+                prev_skip = true;
+            }
         } else if (ragged) {
 #pragma unroll 2
             for (int u = 0; u < CHUNK; u++)
@@ -423,6 +537,7 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
             for (int u = 0; u < CHUNK; u++)
                 wave_step<R, SW, PROFILE, false, TRACK, false, PRUNE>(st, lds, u, lane, jl, n, nvalid, 63, R - 1, feed, c1, &cm);
         }
+        if (WINDOW && !skip) { prev_skip = false; void_from = 0x7fffffff; }   // a computed chunk: its output is no constant
         if (NWP) {
             // what the lane can hand on, as below; after a skipped slab it holds nothing
             lane_entry = skip ? NEG_INF : max(cm, masked ? lane_entry : NEG_INF);
@@ -478,9 +593,14 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
             int done = col0 - emit_lane + CHUNK;
             if (done > n) done = n;
             if (done < 0) done = 0;
+            // (window: the last word of a strip that walked to the end -- done, and void from there on)
+            if (WINDOW && c == nchunks - 1) done = WIN_RETIRED + min(void_from, n);
             if (lane == 0) st_agent(prog_out, done);
         }
     }
+    // (window: a retired strip's last word.  Every store of the chunks before it was drained ahead of their own flag, and
+    //  nothing has been stored since; the columns from its first unwritten one on -- col0 - 63 >= void_from -- stay as they are)
+    if (WINDOW && retired && lane == 0) st_agent(prog_out, WIN_RETIRED + void_from);
 
     if (PRUNE && pruned_slabs > 0 && lane == 0 && a->pruned_slabs != nullptr) atomicAdd(a->pruned_slabs, (unsigned long long) pruned_slabs);
     DBG(3, 40);
@@ -529,7 +649,7 @@ __device__ __attribute__((noinline)) void process_strip(const KernelArgs* ap, co
 #ifndef SW32_WAVES_PER_SIMD
 #define SW32_WAVES_PER_SIMD 2
 #endif
-template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false, bool GOAL = false, bool EDGE = false>
+template <int R, bool SW, bool PROFILE, bool TRACK, bool PRUNE = false, bool GOAL = false, bool EDGE = false, bool WINDOW = false>
 __global__ void __launch_bounds__(64)
 #if SW32_WAVES_PER_SIMD == 2
 __attribute__((amdgpu_waves_per_eu(R == 16 ? 1 : 2, R == 16 ? 1 : 2)))
@@ -558,7 +678,7 @@ sw_strip_kernel(const KernelArgs* __restrict__ ap) {
             __builtin_amdgcn_wave_barrier();
             break;
         } else {
-            process_strip<R, SW, PROFILE, TRACK, PRUNE, GOAL, EDGE>(ap, s, lds, lane);
+            process_strip<R, SW, PROFILE, TRACK, PRUNE, GOAL, EDGE, WINDOW>(ap, s, lds, lane);
         }
         complete_strip_common(ap, s, lane, 64 * R, true);
     }
@@ -586,7 +706,18 @@ __global__ void fill_cells_kernel(int2* p, long long count, int2 value) {
 }
 
 template <int R>
-static hipError_t launch_r(const KernelArgs* a, int grid, hipStream_t stream, bool sw, bool profile, bool track, bool prune, bool goal, bool edge) {
+static hipError_t launch_r(const KernelArgs* a, int grid, hipStream_t stream, bool sw, bool profile, bool track, bool prune, bool goal, bool edge, bool window) {
+    if (prune && window) {    // the windowed twin of every pruning instantiation below (MI355SW_F_INT32_WINDOW)
+#define LAUNCH_W(SWV, TRV, GOV, EDV) do { \
+        if (profile) hipLaunchKernelGGL((sw_strip_kernel<R, SWV, true, TRV, true, GOV, EDV, true>), dim3(grid), dim3(64), 0, stream, a); \
+        else hipLaunchKernelGGL((sw_strip_kernel<R, SWV, false, TRV, true, GOV, EDV, true>), dim3(grid), dim3(64), 0, stream, a); } while (0)
+        if (sw) LAUNCH_W(true, true, false, false);
+        else if (goal) LAUNCH_W(false, false, true, false);
+        else if (edge) LAUNCH_W(false, false, false, true);
+        else LAUNCH_W(false, false, false, false);
+#undef LAUNCH_W
+        return hipGetLastError();
+    }
 #define LAUNCH(SWV, PRV, TRV) \
     hipLaunchKernelGGL((sw_strip_kernel<R, SWV, PRV, TRV>), dim3(grid), dim3(64), 0, stream, a)
     if (sw && prune) {        // block pruning: local alignments with their best score tracked
@@ -613,7 +744,7 @@ static hipError_t launch_r(const KernelArgs* a, int grid, hipStream_t stream, bo
 }
 
 hipError_t launch_strip_kernel(const KernelArgs& a, KernelArgs* dargs, int rows_per_lane, int grid, hipStream_t stream,
-                               bool sw, bool profile, bool track) {
+                               bool sw, bool profile, bool track, bool window) {
     hipError_t e = hipMemcpyAsync(dargs, &a, sizeof(KernelArgs), hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) return e;
     e = hipStreamSynchronize(stream);      // `a` is a host temporary
@@ -624,10 +755,11 @@ hipError_t launch_strip_kernel(const KernelArgs& a, KernelArgs* dargs, int rows_
     const bool goal = prune && (a.goal_bound_col > NEG_INF / 2 || a.goal_bound_row > NEG_INF / 2);
     const bool edge = prune && !goal && a.prune_end != 0;
     if ((goal || edge) && (track || sw)) return hipErrorInvalidValue;
+    if (window && !prune) return hipErrorInvalidValue;    // (the window is the pruning kernels': a missing kernel is an error)
     switch (rows_per_lane) {
-    case 4: return launch_r<4>(dargs, grid, stream, sw, profile, track, prune, goal, edge);
-    case 8: return launch_r<8>(dargs, grid, stream, sw, profile, track, prune, goal, edge);
-    case 16: return launch_r<16>(dargs, grid, stream, sw, profile, track, prune, goal, edge);
+    case 4: return launch_r<4>(dargs, grid, stream, sw, profile, track, prune, goal, edge, window);
+    case 8: return launch_r<8>(dargs, grid, stream, sw, profile, track, prune, goal, edge, window);
+    case 16: return launch_r<16>(dargs, grid, stream, sw, profile, track, prune, goal, edge, window);
     default: return hipErrorInvalidValue;
     }
 }

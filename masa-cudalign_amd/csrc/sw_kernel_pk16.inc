@@ -215,7 +215,7 @@ enum { WIN = 128 };   // seq1 window: 128 columns of history in front of the 64-
 // predecessor's gap in one step when its own state is void, and retires at once when it is void behind the
 // predecessor's X: strips below the end of the alignment end after three chunks instead of walking the whole width.
 // Rows that must exist in memory (special rows, checkpoint rows, the last row) are pre-filled with the constant by the host.
-#define WIN_RETIRED 0x40000000
+// (WIN_RETIRED itself: sw_kernel.h -- the int32 family's window reads the progress word the same way)
 
 struct __attribute__((aligned(16))) WaveLds16 {
     int2 in_tf[CHUNK + (PK16_LDS_AHEAD > 2 ? PK16_LDS_AHEAD : 2)];      // (T16<<16, F16<<16) of the row above (value in the HIGH half: DPP `old` of lane 0)

@@ -35,6 +35,7 @@ F_STREAM_GAP_COLUMNS = 8192        # gap-initialised first columns taken from th
 F_WIDE_ALPHABET = 65536            # pairs with 15 to 62 common byte values run on the packed kernels' wide-alphabet twins (off: int32 kernels)
 F_INT32_PRUNE_GLOBAL = 131072     # block pruning of global alignments (last-cell rule) on the int32 kernel family too (off: every cell computed)
 F_INT32_PRUNE_EDGE_GOAL = 262144  # the edge rule (setPruneEnd) and goal bounds (setGoalBounds) on the int32 kernel family too (off: every cell computed)
+F_INT32_WINDOW = 524288           # the pruning window (retire behind the alignment) on the int32 kernel family, wherever it prunes (off: every strip walks the width)
 V_MESSAGES, V_JOBS, V_SEED_TILES, V_BATCH, V_DEBUG_WORDS = 1, 2, 4, 8, 16
 
 # The C library reads no environment variable (ABI 7): the MI355SW_* switches live HERE, in the Python front, and are
@@ -45,7 +46,8 @@ _ENV_FLAGS = {"MI355SW_NO_DIAGONAL_SEED": F_NO_DIAGONAL_SEED, "MI355SW_NOSEED": 
               "MI355SW_NO_BATCH": F_NO_BATCH, "MI355SW_NOHOST": F_NO_HOST_COUNTER, "MI355SW_NO_WINDOW": F_NO_WINDOW, "MI355SW_STAIRCASE_SEED": F_STAIRCASE_SEED,
               "MI355SW_STREAM_GAP_COLUMNS": F_STREAM_GAP_COLUMNS, "MI355SW_DETERMINISTIC_PRUNE": F_DETERMINISTIC_PRUNE,
               "MI355SW_NO_GOAL_SWEEP_HEIGHTS": F_NO_GOAL_SWEEP_HEIGHTS, "MI355SW_WIDE_ALPHABET": F_WIDE_ALPHABET,
-              "MI355SW_INT32_PRUNE_GLOBAL": F_INT32_PRUNE_GLOBAL, "MI355SW_INT32_PRUNE_EDGE_GOAL": F_INT32_PRUNE_EDGE_GOAL}
+              "MI355SW_INT32_PRUNE_GLOBAL": F_INT32_PRUNE_GLOBAL, "MI355SW_INT32_PRUNE_EDGE_GOAL": F_INT32_PRUNE_EDGE_GOAL,
+              "MI355SW_INT32_WINDOW": F_INT32_WINDOW}
 _ENV_VERBOSITY = {"MI355SW_VERBOSE": V_MESSAGES, "MI355SW_VERBOSE_JOBS": V_JOBS, "MI355SW_VERBOSE_TILES": V_SEED_TILES,
                   "MI355SW_BATCH_DEBUG": V_BATCH, "MI355SW_DEBUG": V_DEBUG_WORDS}
 

@@ -26,6 +26,8 @@ MI355X) behind the handful of MASA-CUDAlign options that concern the path -- not
                                 (MI355SW_F_INT32_PRUNE_GLOBAL; same alignment, off by default)
       --int32-prune-edge-goal   with --prune-edges / --prune-traceback: sequences that run on the int32 kernels prune by the edge
                                 rule and stage 2's goal bounds too (MI355SW_F_INT32_PRUNE_EDGE_GOAL; same alignment, off by default)
+      --int32-window            sequences that run on the int32 kernels prune with the pruning window: strips below the end of the
+                                alignment retire instead of walking the width (MI355SW_F_INT32_WINDOW; same alignment, off by default)
 
 Prints one JSON line (best score, crosspoints per stage, seconds per stage) and leaves alignment.00.txt in the work
 directory.  The engine has no CPU fallback: without an MI355X this fails with MI355SW_ENOGPU."""
@@ -53,7 +55,7 @@ def main(argv):
             "+": pkg.AT_SEQUENCE_1_AND_2}
     work, limit, device, prune, only1, edges, count, ram = "./work.tmp", None, 0, True, False, "**", 1, 0
     trim, rev, comp, clear_n = [0, 0, 0, 0], [False, False], [False, False], False
-    prune_global = prune_traceback = wide_alphabet = prune_edges = int32_prune_global = int32_prune_edge_goal = False
+    prune_global = prune_traceback = wide_alphabet = prune_edges = int32_prune_global = int32_prune_edge_goal = int32_window = False
     weights = None
     resume = False
     files = []
@@ -92,6 +94,8 @@ def main(argv):
             int32_prune_global = True
         elif a == "--int32-prune-edge-goal":
             int32_prune_edge_goal = True
+        elif a == "--int32-window":
+            int32_window = True
         elif a.startswith("--split="):
             v = [int(x) for x in a[8:].split(",")]
             weights = [1] * v[0] if len(v) == 1 else v
@@ -113,7 +117,8 @@ def main(argv):
         limit = min((len(seqs[0]) // 8192 + 2) * (len(seqs[1]) + 1) * 8, 4 << 30)
     al = pkg.MI355Aligner(device=device, flags=(pkg.engine.F_WIDE_ALPHABET if wide_alphabet else 0) |
                           (pkg.engine.F_INT32_PRUNE_GLOBAL if int32_prune_global else 0) |
-                          (pkg.engine.F_INT32_PRUNE_EDGE_GOAL if int32_prune_edge_goal else 0))
+                          (pkg.engine.F_INT32_PRUNE_EDGE_GOAL if int32_prune_edge_goal else 0) |
+                          (pkg.engine.F_INT32_WINDOW if int32_window else 0))
     try:
         if only1:
             bounds = (seqs[0].offset0 - 1, seqs[1].offset0 - 1, seqs[0].offset1, seqs[1].offset1)
